@@ -15,7 +15,7 @@ are exact int64 fixed point of the fp32 rows (dtype "fp32"); ``--no-exact``
 runs the bf16-input variant.  Data: synthetic Gaussian mixture generated in HBM by the
 framework's own split loader; centroids initialised from the first k points.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (N > 1, one rank per GPU)
 
 With ``--gpus N > 1`` and no torchrun environment, bench.py launches the N rank
@@ -34,6 +34,13 @@ synchronize), K timed iteration jobs, another barrier job.  Rank 0 hosts the
 JobTracker and client and observes the completion of every job, which
 requires every rank's reduce to have finished, so its wall time is the max over
 ranks.
+
+A plain run does only that: set up, warm up, time the K jobs, print the result
+line (every figure in it is a by-product of the timed jobs).  ``--dump-outputs
+DIR`` then also writes what the last timed job returned (its centroids, shift
+and point count) as ``DIR/<name>.npy``.  ``--full`` is where measurements that
+need runs of their own belong; this benchmark has none today (the per-config
+and per-kernel ones are separate tools under ``tools/``), so it adds nothing.
 """
 from __future__ import annotations
 
@@ -83,6 +90,14 @@ def main():
     ap.add_argument("--input", default=None, metavar="DIR",
                     help="SequenceFile input (tools/write_kmeans_input.py writes the synthetic "
                          "set as files) instead of points generated in HBM")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed iteration job "
+                         "returned as DIR/<name>.npy: centroids (k x dims, float32), shift and "
+                         "points (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need.  This benchmark has "
+                         "no such extra measurement (the per-config and per-kernel ones are "
+                         "tools/bench_*.py and tools/kbench_*.py), so the option changes nothing")
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("-D", dest="defines", action="append", default=[], metavar="KEY=VALUE",
                     help="extra configuration (e.g. -D hbmr.gpu.first.chunk=8)")
@@ -129,6 +144,14 @@ def main():
     # its synchronisation happen in the workers (the barrier job synchronises
     # every worker's device), and this process never holds a HIP context
     has_gpu = torch.cuda.device_count() > 0 and a.simulate_ms is None
+    if has_gpu:
+        # the map and reduce kernels are the native library's (hbmr/lib/libhbmr.so);
+        # with GPU worker processes it is they that call them, so a missing or
+        # stale build would only show once a worker had started.  Loaded here
+        # first, it is an error at once (loading registers the code objects and
+        # creates no HIP context)
+        from hbmr.ops import _lib
+        _lib.load()
     in_process = a.in_process and has_gpu
     # (a simulated run may also keep its simulated slots in the tracker process)
     conf.set_boolean("hbmr.gpu.worker.process", not (in_process or a.in_process))
@@ -202,6 +225,8 @@ def main():
         jt_thr = {k: round((v - jt_thr0.get(k, 0.0)) / a.steps * 1e3, 3)
                   for k, v in node.jt.thread_cpu().items()} if jt_proc else None
         hist = drv.history[a.warmup:]
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, drv)
         if a.verbose:
             J = "org.apache.hadoop.mapred.JobInProgress$Counter"
             for i, h in enumerate(drv.history):
@@ -310,6 +335,32 @@ def main():
             dump_profiles(cprof)
         node.shutdown()
     return 0
+
+
+def dump_outputs(path, drv):
+    """``--dump-outputs``: what the last iteration job gave its caller, as
+    ``<path>/<name>.npy``: ``centroids`` (k x dims, float32: the version the
+    reduce committed to the driver's centroid directory before it reported
+    success, or the one that came back with the result), and the result's
+    ``shift`` and ``points`` (float64, one element each).  The input is the
+    seeded synthetic set (or the given files), so equal arguments give equal
+    inputs from run to run."""
+    import numpy as np
+
+    from hbmr.models.kmeans import _centroid_file
+    last = drv.history[-1]
+    saved = _centroid_file(drv.centroid_dir, last["centroids_key"])
+    if os.path.exists(saved):
+        cen = np.load(saved)
+    else:
+        c = drv.centroids()
+        if c is None:
+            raise RuntimeError(f"--dump-outputs: centroids {last['centroids_key']} not found")
+        cen = c[:, :drv.d].numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "centroids.npy"), np.ascontiguousarray(cen, dtype=np.float32))
+    np.save(os.path.join(path, "shift.npy"), np.array([last["shift"]], dtype=np.float64))
+    np.save(os.path.join(path, "points.npy"), np.array([last["points"]], dtype=np.float64))
 
 
 def spawn_ranks(n):

@@ -99,11 +99,18 @@ def test_cluster_job_uses_memory_outputs_and_purges_them(tmp_path, monkeypatch):
         # every map's output was held in memory (3 input files -> 3 maps)
         assert len(held) == 3 and all(ok and jid in p for p, ok in held)
         # the finished job is purged from the trackers (its kill action rides
-        # on their next heartbeats)
+        # on their next heartbeats).  Only this cluster's entries are looked at:
+        # the store is the process's, and job ids repeat between clusters
+        # started in the same minute (an earlier test's cluster may have shut
+        # down with a job of the same id still held)
+        def mine():
+            return [p for p in list(mapoutput.STORE._d)
+                    if p.startswith(cl.local_dir + "/") and jid in p]
+        assert all(p.startswith(cl.local_dir + "/") for p, _ok in held)
         end = time.time() + 10
-        while time.time() < end and any(jid in p for p in mapoutput.STORE._d):
+        while time.time() < end and mine():
             time.sleep(0.05)
-        assert not any(jid in p for p in mapoutput.STORE._d)
+        assert not mine()
         # (the same job with the store off writes files)
         wc.set_long(mapoutput.MAX_KEY, 0)
         job = wordcount.make_job(str(inp), str(tmp_path / "out2"), reduces=2, conf=wc)
