@@ -1,10 +1,15 @@
 """Grep: count regex matches, then sort by count descending
 (src/examples/org/apache/hadoop/examples/Grep.java: a RegexMapper +
 LongSumReducer job into a temp SequenceFile, then an InverseMapper sort job
-with LongWritable.DecreasingComparator and one reducer)."""
+with LongWritable.DecreasingComparator and one reducer).
+
+``-gpu`` runs the search job as the split-level job of hbmr/models/grep.py
+(DFA regex kernels on the GPU map slots); the sort job is the same.  A pattern
+the GPU matcher does not take logs the reason and runs the classic search."""
 from __future__ import annotations
 
 import argparse
+import logging
 import os
 import shutil
 import tempfile
@@ -14,6 +19,8 @@ from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf
 from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
 from ..mapred.lib.basic import InverseMapper, LongSumReducer, RegexMapper
 
+log = logging.getLogger("hbmr.examples.grep")
+
 
 class DecreasingLong:
     """LongWritable.DecreasingComparator as a sort key over serialised keys."""
@@ -22,38 +29,71 @@ class DecreasingLong:
         return -int.from_bytes(kb[:8], "big", signed=True)
 
 
-def run(inp, out, regex, group=0, conf=None, cluster=None, verbose=False):
+def _search_gpu(inp, out, regex, group, conf, cluster):
+    """The search job as a split job; False if the pattern is not eligible."""
+    from ..models import grep as G
+    try:
+        job = G.gpu_job(inp, out, regex, group, base=conf)
+    except ValueError as e:
+        log.warning("%s; running the classic search job", e)
+        return False
+    own = cluster is None
+    if own:
+        import torch
+        from ..mapred.cluster import LocalCluster
+        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
+        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
+    try:
+        rj = cluster.submit_job(job)
+        rj.waitForCompletion()
+        if not rj.isSuccessful():
+            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
+    finally:
+        if own:
+            cluster.shutdown()
+    return True
+
+
+def run(inp, out, regex, group=0, conf=None, cluster=None, verbose=False, gpu=False):
     tmp = tempfile.mkdtemp(prefix="grep-temp-")
     try:
-        grep = JobConf(conf)
-        grep.set_job_name("grep-search")
-        FileInputFormat.setInputPaths(grep, *([inp] if isinstance(inp, str) else inp))
-        grep.set_mapper_class(RegexMapper)
-        grep.set("mapred.mapper.regex", regex)
-        grep.set_int("mapred.mapper.regex.group", group)
-        grep.set_combiner_class(LongSumReducer)
-        grep.set_reducer_class(LongSumReducer)
-        FileOutputFormat.setOutputPath(grep, os.path.join(tmp, "out"))
-        grep.set_output_format(SequenceFileOutputFormat)
-        grep.set_output_key_class(Text)
-        grep.set_output_value_class(LongWritable)
-        JobClient.runJob(grep, cluster=cluster, verbose=verbose)
-
-        sort = JobConf(conf)
-        sort.set_job_name("grep-sort")
-        FileInputFormat.setInputPaths(sort, os.path.join(tmp, "out"))
-        sort.set_input_format(SequenceFileInputFormat)
-        sort.set_mapper_class(InverseMapper)
-        sort.set_num_reduce_tasks(1)
-        FileOutputFormat.setOutputPath(sort, out)
-        sort.set_map_output_key_class(LongWritable)
-        sort.set_map_output_value_class(Text)
-        sort.set_output_key_class(LongWritable)
-        sort.set_output_value_class(Text)
-        sort.set_output_key_comparator_class(DecreasingLong)
-        return JobClient.runJob(sort, cluster=cluster, verbose=verbose)
+        if not (gpu and _search_gpu(inp, os.path.join(tmp, "out"), regex, group, conf, cluster)):
+            _search(inp, os.path.join(tmp, "out"), regex, group, conf, cluster, verbose)
+        return _sort(os.path.join(tmp, "out"), out, conf, cluster, verbose)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+def _search(inp, out, regex, group, conf, cluster, verbose):
+    grep = JobConf(conf)
+    grep.set_job_name("grep-search")
+    FileInputFormat.setInputPaths(grep, *([inp] if isinstance(inp, str) else inp))
+    grep.set_mapper_class(RegexMapper)
+    grep.set("mapred.mapper.regex", regex)
+    grep.set_int("mapred.mapper.regex.group", group)
+    grep.set_combiner_class(LongSumReducer)
+    grep.set_reducer_class(LongSumReducer)
+    FileOutputFormat.setOutputPath(grep, out)
+    grep.set_output_format(SequenceFileOutputFormat)
+    grep.set_output_key_class(Text)
+    grep.set_output_value_class(LongWritable)
+    JobClient.runJob(grep, cluster=cluster, verbose=verbose)
+
+
+def _sort(inp, out, conf, cluster, verbose):
+    sort = JobConf(conf)
+    sort.set_job_name("grep-sort")
+    FileInputFormat.setInputPaths(sort, inp)
+    sort.set_input_format(SequenceFileInputFormat)
+    sort.set_mapper_class(InverseMapper)
+    sort.set_num_reduce_tasks(1)
+    FileOutputFormat.setOutputPath(sort, out)
+    sort.set_map_output_key_class(LongWritable)
+    sort.set_map_output_value_class(Text)
+    sort.set_output_key_class(LongWritable)
+    sort.set_output_value_class(Text)
+    sort.set_output_key_comparator_class(DecreasingLong)
+    return JobClient.runJob(sort, cluster=cluster, verbose=verbose)
 
 
 def main(argv=None, cluster=None):
@@ -62,6 +102,8 @@ def main(argv=None, cluster=None):
     ap.add_argument("outdir")
     ap.add_argument("regex")
     ap.add_argument("group", nargs="?", type=int, default=0)
+    ap.add_argument("-gpu", action="store_true",
+                    help="run the search as a split-level job (DFA regex kernels on GPU slots)")
     a = ap.parse_args(argv)
-    rj = run(a.indir, a.outdir, a.regex, a.group, cluster=cluster, verbose=True)
+    rj = run(a.indir, a.outdir, a.regex, a.group, cluster=cluster, verbose=True, gpu=a.gpu)
     return 0 if rj.isSuccessful() else 1

@@ -150,6 +150,23 @@ _SIGS = {
                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hbmr_wc_pack": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
                              c_void_p]),
+    # grep (native/kernels/grep.hip)
+    "hbmr_grep_cand_count": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p]),
+    "hbmr_grep_cand_write": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hbmr_grep_select_blocks": (c_long, [c_long]),
+    "hbmr_grep_block_max": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_grep_prefix_max": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "hbmr_grep_select_count": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_grep_select_write": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]),
+    "hbmr_span_insert": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                 c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_span_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hbmr_lines_count": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_lines_write": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

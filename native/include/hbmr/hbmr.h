@@ -194,6 +194,39 @@ int hbmr_wc_pack(const uint8_t* buf, const uint32_t* ustart, const uint32_t* ule
                  const int64_t* order, long nu, const int64_t* out_off, uint8_t* out,
                  hipStream_t st);
 #endif
+// ---- grep (native/kernels/grep.hip) ---------------------------------------------
+#ifndef HBMR_NO_HIP_DECLS
+// table[nstates·nclasses]: next state | 0x8000 if it accepts; state 0 is dead, the
+// last class is the synthetic end of line.  Tiles are hbmr_wc_tiles(n).
+int hbmr_grep_cand_count(const uint8_t* buf, long n, const uint16_t* table,
+                         const uint8_t* byteclass, int nstates, int nclasses, int start_bol,
+                         int start_mid, uint32_t* tile_counts, int* non_ascii, hipStream_t st);
+int hbmr_grep_cand_write(const uint8_t* buf, long n, const uint16_t* table,
+                         const uint8_t* byteclass, int nstates, int nclasses, int start_bol,
+                         int start_mid, const long* tile_base, uint32_t* pos, uint32_t* len,
+                         int64_t* end, hipStream_t st);
+// pmax[j] = max end of candidates 0..j: a maximum per block of hbmr_grep_select_blocks,
+// the caller's scan of those into block_prefix (max of the blocks before), the rewrite
+long hbmr_grep_select_blocks(long nc);
+int hbmr_grep_block_max(const int64_t* end, long nc, int64_t* block_max, hipStream_t st);
+int hbmr_grep_prefix_max(const int64_t* end, long nc, const int64_t* block_prefix, int64_t* pmax,
+                         hipStream_t st);
+int hbmr_grep_select_count(const uint32_t* pos, const uint32_t* len, const int64_t* pmax, long nc,
+                           uint32_t* block_counts, hipStream_t st);
+int hbmr_grep_select_write(const uint32_t* pos, const uint32_t* len, const int64_t* pmax, long nc,
+                           const long* block_base, uint32_t* spos, uint32_t* slen,
+                           hipStream_t st);
+int hbmr_span_insert(const uint8_t* buf, long n, const uint32_t* starts, const uint32_t* lens,
+                     const int64_t* weights, long nspans, uint64_t* tkeys, uint64_t* tcounts,
+                     long cap, int* overflow, hipStream_t st);
+int hbmr_span_compact(const uint8_t* buf, const uint32_t* starts, const uint32_t* lens,
+                      const uint64_t* tkeys, const uint64_t* tcounts, long cap, int R,
+                      uint32_t* ustart, uint32_t* ulen, int64_t* ucount, int32_t* upart,
+                      unsigned int* counter, hipStream_t st);
+int hbmr_lines_count(const uint8_t* buf, long n, uint32_t* tile_counts, hipStream_t st);
+int hbmr_lines_write(const uint8_t* buf, long n, const long* tile_base, uint32_t* starts,
+                     uint32_t* lens, hipStream_t st);
+#endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
 long hbmr_kmeans_batch_workspace_bytes(long total_n, int ntasks, int k);
