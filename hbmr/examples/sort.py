@@ -1,10 +1,16 @@
 """Sort: identity map/reduce over SequenceFiles, optionally totally ordered
 (src/examples/org/apache/hadoop/examples/Sort.java: -inFormat/-outFormat,
 -outKey/-outValue, -r reduces, -totalOrder pcnt numSamples maxSplits →
-InputSampler.RandomSampler + TotalOrderPartitioner)."""
+InputSampler.RandomSampler + TotalOrderPartitioner).
+
+``-gpu`` runs the job as the split-level job of hbmr/models/sort.py (record
+sort kernels on the GPU map slots); with ``-totalOrder`` the partition file is
+sampled as always and its keys are the split points.  An input the GPU sort
+does not take logs the reason and runs the classic job."""
 from __future__ import annotations
 
 import argparse
+import logging
 import os
 
 from ..io import sequencefile as seqf
@@ -12,6 +18,8 @@ from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf
 from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
 from ..mapred.lib.basic import IdentityMapper, IdentityReducer, InputSampler, TotalOrderPartitioner
 from ..utils.reflection import load_class
+
+log = logging.getLogger("hbmr.examples.sort")
 
 
 def make_job(inp, out, reduces=1, total_order=None, conf=None, in_format=None,
@@ -42,6 +50,43 @@ def make_job(inp, out, reduces=1, total_order=None, conf=None, in_format=None,
     return job
 
 
+def _sort_gpu(job, inp, out, reduces, conf, cluster, in_format, out_format):
+    """The sort as a split job (partition file and split points of ``job``, the
+    classic job already made); None if the input is not eligible."""
+    from ..models import sort as S
+    try:
+        gjob = S.gpu_job(inp, out, reduces, job.get("total.order.partitioner.path"), base=conf,
+                         in_format=in_format, out_format=out_format)
+    except ValueError as e:
+        log.warning("%s; running the classic sort job", e)
+        return None
+    own = cluster is None
+    if own:
+        import torch
+        from ..mapred.cluster import LocalCluster
+        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
+        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
+    try:
+        rj = cluster.submit_job(gjob)
+        rj.waitForCompletion()
+        if not rj.isSuccessful():
+            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
+    finally:
+        if own:
+            cluster.shutdown()
+    return rj
+
+
+def run(inp, out, reduces=1, total_order=None, conf=None, cluster=None, in_format=None,
+        out_format=None, gpu=False):
+    """Run the sort; ``gpu``: as the split-level job of hbmr/models/sort.py
+    (record sort kernels on the GPU map slots), the classic job if the input
+    is not eligible (the reason is logged)."""
+    job = make_job(inp, out, reduces, total_order, conf, in_format, out_format)
+    rj = _sort_gpu(job, inp, out, reduces, conf, cluster, in_format, out_format) if gpu else None
+    return rj if rj is not None else JobClient.runJob(job, cluster=cluster)
+
+
 def _first_file(inp):
     p = inp if isinstance(inp, str) else inp[0]
     if os.path.isdir(p):
@@ -58,12 +103,13 @@ def main(argv=None, cluster=None):
     ap.add_argument("-inFormat")
     ap.add_argument("-outFormat")
     ap.add_argument("-totalOrder", nargs=3, metavar=("pcnt", "numSamples", "maxSplits"))
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a split-level job (record sort kernels on GPU slots)")
     a = ap.parse_args(argv)
     to = None
     if a.totalOrder:
         to = (float(a.totalOrder[0]), int(a.totalOrder[1]), int(a.totalOrder[2]))
-    job = make_job(a.indir, a.outdir, a.r, to,
-                   in_format=load_class(a.inFormat) if a.inFormat else None,
-                   out_format=load_class(a.outFormat) if a.outFormat else None)
-    rj = JobClient.runJob(job, cluster=cluster)
+    rj = run(a.indir, a.outdir, a.r, to, cluster=cluster,
+             in_format=load_class(a.inFormat) if a.inFormat else None,
+             out_format=load_class(a.outFormat) if a.outFormat else None, gpu=a.gpu)
     return 0 if rj.isSuccessful() else 1

@@ -154,6 +154,24 @@ class Writer:
         self.out.write(kb)
         self.out.write(vb)
 
+    def append_frames(self, body, gaps):
+        """Write a body of record frames (``[recordLen][keyLen][key][value]``,
+        uncompressed files only) laid out for this file's current position by
+        ``hbmr.ops.recsort.layout``: ``body`` (a writable uint8 numpy array or
+        bytearray) has a 20-byte hole at each offset of ``gaps``, filled here
+        with the sync escape and this file's sync marker — the bytes
+        ``append_raw`` would have written for the same records."""
+        if self.compression != NONE:
+            raise ValueError("append_frames writes uncompressed records")
+        view = memoryview(body).cast("B")
+        esc = struct.pack(">i", SYNC_ESCAPE) + self.sync
+        base = self.out.tell()
+        for g in gaps:
+            g = int(g)
+            view[g:g + SYNC_SIZE] = esc
+            self.last_sync_pos = base + g + SYNC_SIZE
+        self.out.write(view)
+
     def _flush_block(self):
         if self._blk_n == 0:
             return

@@ -167,6 +167,21 @@ _SIGS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hbmr_lines_count": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_lines_write": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # record sort (native/kernels/recsort.hip)
+    "hbmr_recsort_hash_partition": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p,
+                                            c_void_p]),
+    "hbmr_recsort_round_keys": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int,
+                                        c_void_p, c_void_p, c_void_p]),
+    "hbmr_recsort_round_workspace_bytes": (c_long, [c_long]),
+    "hbmr_recsort_round": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_long, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_long, c_void_p]),
+    "hbmr_recsort_cuts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "hbmr_recsort_chunk_bytes": (c_int, []),
+    "hbmr_recsort_set_chunk_lanes": (c_int, [c_int]),
+    "hbmr_recsort_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_long, c_long, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -226,6 +226,31 @@ int hbmr_span_compact(const uint8_t* buf, const uint32_t* starts, const uint32_t
 int hbmr_lines_count(const uint8_t* buf, long n, uint32_t* tile_counts, hipStream_t st);
 int hbmr_lines_write(const uint8_t* buf, long n, const long* tile_base, uint32_t* starts,
                      uint32_t* lens, hipStream_t st);
+// ---- record sort (native/kernels/recsort.hip) --------------------------------
+// Records of a byte buffer by index arrays (int64[n] each): frame offset/length,
+// key payload offset/length.  part[i] = (hashBytes(payload) & INT_MAX) % nparts
+int hbmr_recsort_hash_partition(const uint8_t* data, const int64_t* koff, const int64_t* klen,
+                                long n, int nparts, uint32_t* part, hipStream_t st);
+// keys[i] = (payload[7d : 7d+7] zero-padded, big-endian) << 8 | min(len - 7d, 8) of
+// record rec[i]; vals[i] = i
+int hbmr_recsort_round_keys(const uint8_t* data, const int64_t* koff, const int64_t* klen,
+                            const uint32_t* rec, long m, int d, uint64_t* keys, uint32_t* vals,
+                            hipStream_t st);
+long hbmr_recsort_round_workspace_bytes(long m);
+int hbmr_recsort_round(const uint8_t* data, const int64_t* koff, const int64_t* klen, int d,
+                       long m, int seg_bits, const uint32_t* act_pos, const uint32_t* act_rec,
+                       const uint32_t* act_seg, uint32_t* perm, uint32_t* new_pos,
+                       uint32_t* new_rec, uint32_t* new_seg, uint32_t* count, void* ws,
+                       long ws_bytes, hipStream_t st);
+int hbmr_recsort_cuts(const uint8_t* data, const int64_t* koff, const int64_t* klen,
+                      const uint32_t* perm, long n, const uint8_t* sp, const int64_t* sp_off,
+                      const int64_t* sp_len, int nsplit, int64_t* cuts, hipStream_t st);
+int hbmr_recsort_chunk_bytes(void);
+int hbmr_recsort_set_chunk_lanes(int lanes);
+int hbmr_recsort_gather(const uint8_t* src, const uint32_t* perm, const int64_t* foff,
+                        const int64_t* flen, const int64_t* dst_off, const int64_t* chunk_base,
+                        const uint32_t* chunk_entry, long n, long nchunks, uint8_t* dst,
+                        hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
