@@ -63,6 +63,10 @@ EXACT_MFMA_KEY = "hbmr.kmeans.exact.mfma"
 # against the split's reference partition (ops.kmeans.Baseline) — bit-identical
 # to "sorted", the counting-sort combiner over every point
 COMBINER_KEY = "hbmr.kmeans.combiner"
+# exact mode with the delta combiner: keep a certified per-point bound on the
+# reference partition and skip the points it proves unchanged (default true;
+# false: every point is assigned every iteration).  Same labels either way.
+BOUNDS_KEY = "hbmr.kmeans.exact.bounds"
 
 # --------------------------------------------------------------------------- data
 _M32 = 0xFFFFFFFF
@@ -263,6 +267,7 @@ def _sum_slabs(outs):
 
 
 _EXACT_STATS: dict = {}
+_EXACT_SKIPPED: dict = {}
 _EXACT_LOCK = threading.Lock()
 
 # Reference partitions of the delta combiner, per (split, device, k, dp,
@@ -305,7 +310,9 @@ def _baseline_plan(ctxs, datas, k, dp, fx, exact, enabled):
 
 
 def _baseline_bytes(b) -> int:
-    return sum(t.numel() * t.element_size() for t in (b.g, b.S0, b.N0) if t is not None)
+    # ref is shared by the splits of a batch (k x d floats): not charged per split
+    return sum(t.numel() * t.element_size() for t in (b.g, b.S0, b.N0, getattr(b, "gap", None))
+               if t is not None)
 
 
 def _drop_baselines(split_key, device):
@@ -317,12 +324,13 @@ def _drop_baselines(split_key, device):
             _BASELINES.pop(key)
 
 
-def _install_baselines(entries, stream, cache=None):
+def _install_baselines(entries, stream, cache=None, grown=None):
     """entries: (key, Baseline) updated or created by a batch just enqueued on
     ``stream``; their event marks its end.  A NEW baseline's device memory is
     charged to its split's entry in the tracker's split cache (``cache``), so
     it counts against hbmr.gpu.hbm.reserve.gb's capacity and is dropped when
-    the split is evicted."""
+    the split is evicted; so are the bytes an installed one grew by in this
+    batch (``grown``: id(baseline) -> bytes, its new per-point bounds)."""
     ev = torch.cuda.Event()
     ev.record(stream)
     charge = []
@@ -332,14 +340,16 @@ def _install_baselines(entries, stream, cache=None):
             old = _BASELINES.pop(key, None)
             _BASELINES[key] = b
             if old is not b:
-                charge.append((key, b))
+                charge.append((key, b, _baseline_bytes(b)))
+            elif grown and grown.get(id(b)):
+                charge.append((key, b, grown[id(b)]))
         while len(_BASELINES) > _BASE_MAX:
             _BASELINES.pop(next(iter(_BASELINES)))
     if cache is not None and charge:
         cache.add_listener(_drop_baselines)
         idx = stream.device.index if stream is not None else 0
-        for key, b in charge:
-            if not cache.charge(key[0], idx, _baseline_bytes(b)):
+        for key, b, nbytes in charge:
+            if not cache.charge(key[0], idx, nbytes):
                 # the split is not cache-resident (streamed through): keep no
                 # reference partition HBM the cache cannot account for
                 with _BASE_LOCK:
@@ -354,6 +364,16 @@ def _exact_stats(cin, device):
         t = _EXACT_STATS.get(key)
         if t is None:
             t = _EXACT_STATS[key] = torch.zeros(3, dtype=torch.int64, device=device)
+        return t
+
+
+def _exact_skipped(cin, device):
+    """Device counter of the points the bounded assign skipped in one iteration."""
+    key = (cin, str(device))
+    with _EXACT_LOCK:
+        t = _EXACT_SKIPPED.get(key)
+        if t is None:
+            t = _EXACT_SKIPPED[key] = torch.zeros(1, dtype=torch.int64, device=device)
         return t
 
 
@@ -375,6 +395,7 @@ class KMeansSplitJob(SplitJob):
         self.exact = conf.get_boolean(EXACT_KEY, False)
         self.exact_dtype = torch.bfloat16 if (conf.get(EXACT_MFMA_KEY) or "f16").lower() in (
             "bf16", "bfloat16") else torch.float16
+        self.bounds = conf.get_boolean(BOUNDS_KEY, True)
         self.combiner = (conf.get(COMBINER_KEY) or "delta").lower()
         if self.combiner not in ("delta", "sorted"):
             raise ValueError(f"{COMBINER_KEY} must be delta or sorted, not {self.combiner!r}")
@@ -655,6 +676,7 @@ class KMeansSplitJob(SplitJob):
         pos = {i: j for j, i in enumerate(order)}
         H = len(have)
         installed = []
+        grown = None
         if have:
             ns = [datas[i].shape[0] for i in have]
             total = sum(ns)
@@ -664,11 +686,25 @@ class KMeansSplitJob(SplitJob):
             need = km.delta_workspace_bytes(total, H, self.k)
             if scratch.get("dws") is None or scratch["dws"].numel() < need:
                 scratch["dws"] = torch.empty(need, dtype=torch.uint8, device=ctx.device)
-            km.assign_exact_batch([datas[i] for i in have], img, stats, lab, scratch,
-                                  stream=ctx.stream)
             hb = [bases[i] for i in have]
+            bounded = self.bounds and self.combiner == "delta" and km.bounds_supported(img)
+            if bounded:
+                # points whose stored bound outlasts the centroids' shift keep
+                # their label unassigned; the bounds ride on the baselines and
+                # hold for the labels ``g`` only: every exact job over the
+                # split shares the baseline whatever its conf, so a job that
+                # advances ``g`` without them (below) drops them
+                nogap = [b for b in hb if b.gap is None]
+                km.assign_exact_batch([datas[i] for i in have], img, stats, lab, scratch,
+                                      stream=ctx.stream, bounds=hb,
+                                      skipped=_exact_skipped(self.cin, ctx.device))
+                grown = {id(b): b.gap.numel() * b.gap.element_size() for b in nogap}
+            else:
+                km.assign_exact_batch([datas[i] for i in have], img, stats, lab, scratch,
+                                      stream=ctx.stream)
             km.delta_combine([datas[i].x32 for i in have], lab, self.k, sums[:H], counts[:H],
-                             scratch["dws"], hb, fx_shift=img.fx_shift, stream=ctx.stream)
+                             scratch["dws"], hb, fx_shift=img.fx_shift, stream=ctx.stream,
+                             keep_bounds=bounded)
             for i, b in zip(have, hb):
                 b.S0, b.N0 = sums[pos[i]], counts[pos[i]]
                 installed.append((keys[i], b))
@@ -688,7 +724,7 @@ class KMeansSplitJob(SplitJob):
                 b = km.Baseline(lab.clone(), s, c, d.xb.data_ptr(), d.shape[0])
                 installed.append((keys[i], b))
         if installed:
-            _install_baselines(installed, ctx.stream, getattr(ctx, "split_cache", None))
+            _install_baselines(installed, ctx.stream, getattr(ctx, "split_cache", None), grown)
         for c, d in zip(ctxs, datas):
             c.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, d.shape[0])
         return [(sums[pos[i]], counts[pos[i]]) for i in range(B)]
@@ -767,6 +803,8 @@ class KMeansSplitJob(SplitJob):
         # update and the next job's maps were launched)
         est = _EXACT_STATS.pop((self.cin, str(sums.device)), None) \
             if self.exact and sums.device.type == "cuda" else None
+        esk = _EXACT_SKIPPED.pop((self.cin, str(sums.device)), None) \
+            if self.exact and sums.device.type == "cuda" else None
         killed = getattr(ctx, "killed", None)
         if killed is not None and killed():
             raise RuntimeError("reduce killed (collective restart): result not published")
@@ -818,8 +856,12 @@ class KMeansSplitJob(SplitJob):
             vals = [img.shift2.max().double().sqrt(), counts.sum().double()]
             if est is not None:
                 vals += list(est.double().unbind(0))
+            if esk is not None:
+                vals.append(esk[0].double())
             got = torch.stack(vals).tolist()
             shift, npts = got[0], got[1]
+            if esk is not None:
+                ctx.reporter.incrCounter("KMEANS", "EXACT_BOUND_SKIPPED_POINTS", int(got[-1]))
             if est is not None:
                 for name, v in zip(("EXACT_FLAGGED_POINTS", "EXACT_RELABELLED_POINTS",
                                     "EXACT_NEIGHBOUR_SCANS"), got[2:5]):

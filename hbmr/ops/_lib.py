@@ -45,12 +45,21 @@ _SIGS = {
                                                    c_void_p, c_void_p, c_void_p, c_int, c_int,
                                                    c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_kmeans_bound_workspace_bytes": (c_long, [c_long, c_int, c_int]),
+    "hbmr_kmeans_assign_top3_q1_bounded": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int,
+                                                   c_void_p, c_void_p, c_int, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_long, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_kmeans_centroid_nbr": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
     "hbmr_kmeans_image16": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hbmr_kmeans_image16_tiled": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "hbmr_kmeans_set_exact_kernel": (c_int, [c_int]),
+    "hbmr_kmeans_get_exact_kernel": (c_int, []),
     "hbmr_kmeans_refine_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,

@@ -479,16 +479,40 @@ def assign_exact(split: ExactSplit, img: CentroidImage, stats: torch.Tensor,
     return lab
 
 
+def bounds_supported(img: CentroidImage) -> bool:
+    """Whether ``assign_exact_batch(..., bounds=)`` can run for this image: the
+    bounded pass is a form of the grouped, fused v3 assign (dp <= 128), so not
+    where the v2 kernel is selected (hbmr_kmeans_set_exact_kernel(2) /
+    HBMR_EXACT_V3=v2), which has no bounded form."""
+    return REFINE_VERSION >= 3 and img.dp <= 128 and GROUPED_EXACT and FUSED_Q1 and \
+        img.cen.is_cuda and _lib.load().hbmr_kmeans_get_exact_kernel() == 3
+
+
 def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, out: torch.Tensor,
-                       scratch: dict | None = None, stream=None) -> None:
+                       scratch: dict | None = None, stream=None, bounds: list | None = None,
+                       skipped: torch.Tensor | None = None) -> None:
     """Exact labels of a batch of splits, written back to back into ``out``
     (int32 [sum n]): the top-3 assign and the step-1 certification per split
     (the candidate / score / margin scratch shared by every split: one stream
     orders the reuse), then step 2 and the neighbour scan once per up to 64
     splits (refine v3), with the centroid norms / neighbour lists fetched once
-    and the labels written in place."""
+    and the labels written in place.
+
+    ``bounds``: one ``Baseline`` per split (its reference partition).  A point
+    whose stored ``gap`` — a certified lower bound of (distance to the nearest
+    other centroid - distance to its own) against the centroids ``ref`` —
+    exceeds what its own and the farthest-moving centroid moved since keeps
+    its label without a single distance (hbmr_kmeans_assign_top3_q1_bounded);
+    the labels are the same exact arg-min.  Every baseline leaves with ``gap``
+    rewritten for the labels in ``out`` and the centroids of ``img``
+    (``pending``), and with no ``ref``: the bounds count again once ``g`` has
+    advanced to exactly these labels (``delta_combine(..., keep_bounds=True)``),
+    and are lost if anything else happens to ``g`` first or this call raises.
+    ``skipped`` (int64 [1], device) += the points not assigned."""
     if not splits:
         return
+    if bounds is not None and (len(bounds) != len(splits) or not bounds_supported(img)):
+        raise ValueError("bounds: one baseline per split, grouped fused v3 assign (dp <= 128)")
     dev = splits[0].xb.device
     total = sum(sp.shape[0] for sp in splits)
     if out.dtype != torch.int32 or out.numel() < total or not out.is_contiguous():
@@ -519,6 +543,12 @@ def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, ou
         # needs it (after the first top-3 launch: the reduce builds it on its
         # own stream while that assign runs)
         ni, nd, L = (None, None, 0) if grouped else img.neighbors()
+        # the centroids the bounds will refer to: a private copy (the image's
+        # buffers are refreshed in place), made in-stream, shared by the batch
+        newref = None
+        if bounds is not None:
+            img.cen.record_stream(torch.cuda.current_stream())
+            newref = img.cen.clone()
     lib = _lib.load()
     top3 = lib.hbmr_kmeans_assign_top3_f16 if dt == torch.float16 else \
         lib.hbmr_kmeans_assign_top3_bf16
@@ -530,7 +560,9 @@ def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, ou
         group = splits[g0:g0 + MAX_REFINE_BATCH]
         if grouped:
             off += _exact_group(group, img, stats, base + 4 * off, c16, ch, (cn, cmax, ce, cemax),
-                                dt, scratch, stream, lib, st)
+                                dt, scratch, stream, lib, st,
+                                None if bounds is None else bounds[g0:g0 + MAX_REFINE_BATCH],
+                                skipped, newref)
             continue
         rb = _RefineBatch(group, img, stats, scratch, stream) if REFINE_VERSION >= 3 else None
         for i, sp in enumerate(group):
@@ -563,7 +595,69 @@ GROUPED_EXACT = os.environ.get("HBMR_EXACT_GROUPED", "1") != "0"
 FUSED_Q1 = os.environ.get("HBMR_EXACT_FUSED_Q1", "1") != "0"
 
 
-def _exact_group(group, img, stats, labels_ptr, c16, ch, norms, dt, scratch, stream, lib, st):
+def _bounded_group(group, bases, img, labels_ptr, ch, norms, dt, scratch, stream, lib, st, rb,
+                   skipped, newref):
+    """The bounded form of the fused grouped assign (shift, sweep, assign over
+    the lists): see ``assign_exact_batch``.  ``newref``: the batch's copy of
+    ``img.cen``, which the rewritten bounds refer to (``Baseline.pending``)."""
+    B = len(group)
+    ns = [sp.shape[0] for sp in group]
+    N = sum(ns)
+    dev = group[0].xb.device
+    cur = torch.cuda.current_stream() if stream is None else stream
+    with torch.cuda.stream(cur):
+        # the reference partitions may live on another slot's stream (as in
+        # _delta_args); the centroids on a reduce's
+        events, blocks = {}, {}
+        for b in bases:
+            if b.event is not None and b.stream is not None and b.stream != cur:
+                events[id(b.event)] = b.event
+        for ev in events.values():
+            cur.wait_event(ev)
+        for b in bases:
+            if b.gap is None:
+                # an allocation of its own per split: it is charged to the
+                # split's cache entry and has to go when that split is evicted
+                b.gap, b.ref = torch.empty(b.g.numel(), dtype=torch.float32, device=dev), None
+        for b, n in zip(bases, ns):
+            if b.g.numel() != n or b.gap.numel() != n or \
+                    (b.ref is not None and (tuple(b.ref.shape) != tuple(img.cen.shape) or
+                                            not b.ref.is_contiguous())):
+                raise ValueError("bounds: baseline does not match its split / the centroids")
+            for t in (b.g, b.gap, b.ref):
+                if t is not None:
+                    base = t._base if t._base is not None else t
+                    blocks[id(base)] = base
+        for t in blocks.values():
+            t.record_stream(cur)
+        need = int(lib.hbmr_kmeans_bound_workspace_bytes(N, B, img.k))
+        bws = scratch.get("bound_ws")
+        if bws is None or bws.numel() < need:
+            bws = scratch["bound_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    P = ctypes.c_void_p * B
+    cn, cmax, ce, cemax = norms
+    # the gaps are rewritten for THIS batch's labels from here on: they bound
+    # nothing about ``g`` until it has advanced to those labels
+    # (Baseline.labels_advanced), and nothing at all if that never happens
+    refs = [b.ref for b in bases]
+    for b in bases:
+        b.ref = b.pending = None
+    rc = lib.hbmr_kmeans_assign_top3_q1_bounded(
+        B, P(*[sp.xb.data_ptr() for sp in group]), (ctypes.c_long * B)(*ns), img.dp,
+        int(dt == torch.float16), _ptr(img.image16_tiled(dt)), _ptr(ch), img.k_pad, labels_ptr,
+        P(*[sp.xnorm.data_ptr() for sp in group]), P(*[sp.xbn2.data_ptr() for sp in group]),
+        P(*[sp.xerr.data_ptr() for sp in group]), img.d, img.k, _ptr(cn), _ptr(cmax), _ptr(ce),
+        _ptr(cemax), _ptr(rb.ws), rb.ws.numel(), _ptr(rb.pd),
+        P(*[b.g.data_ptr() for b in bases]), P(*[b.gap.data_ptr() for b in bases]),
+        P(*[None if r is None else r.data_ptr() for r in refs]), _ptr(img.cen),
+        _ptr(bws), bws.numel(), _ptr(skipped), st)
+    _lib.check(rc, "hbmr_kmeans_assign_top3_q1_bounded")
+    for b in bases:
+        b.pending = newref
+
+
+def _exact_group(group, img, stats, labels_ptr, c16, ch, norms, dt, scratch, stream, lib, st,
+                 bases=None, skipped=None, newref=None):
     """Top-3 assign and certification of up to 64 splits with grouped launches
     (hbmr_kmeans_assign_top3_grouped, hbmr_kmeans_refine_batch_q1g); labels of
     the group written back to back at ``labels_ptr``.  Returns the row count."""
@@ -574,6 +668,18 @@ def _exact_group(group, img, stats, labels_ptr, c16, ch, norms, dt, scratch, str
     P = ctypes.c_void_p * B
     xs = P(*[sp.xb.data_ptr() for sp in group])
     nsa = (ctypes.c_long * B)(*ns)
+    if bases is not None:
+        rb = _RefineBatch(group, img, stats, scratch, stream)
+        if TRACE.on:
+            TRACE.instant("kmeans.top3_launch", n=B)
+        _bounded_group(group, bases, img, labels_ptr, ch, norms, dt, scratch, stream, lib, st, rb,
+                       skipped, newref)
+        o = 0
+        for i in range(B):
+            rb.labels[i] = labels_ptr + 4 * o
+            o += ns[i]
+        rb.finish()
+        return N
     if FUSED_Q1 and img.dp <= 128:
         # step 1 in the top-3 epilogue: no candidate / score / margin arrays
         rb = _RefineBatch(group, img, stats, scratch, stream)
@@ -672,14 +778,34 @@ class Baseline:
     holds for ANY g, so the map output computed against it is bit-identical to
     the direct combiner's; it only pays off when few points changed label.
     ``event`` marks the end of the batch that last updated it (its stream is
-    ``stream``): a batch on another stream waits for it first."""
-    __slots__ = ("g", "S0", "N0", "event", "stream", "data_ptr", "n")
+    ``stream``): a batch on another stream waits for it first.
+
+    Exact mode's bounded assign (``assign_exact_batch(..., bounds=)``) adds
+    ``gap`` (fp32 [n]): a certified lower bound of min_{j != g(p)} |x_p - c_j|
+    - |x_p - c_g(p)| (distances over the fp32 data), 0 where none is known,
+    against the centroids ``ref`` (fp32 [k, d], a private copy shared by the
+    splits of a batch).  ``ref`` None: ``gap`` (if allocated) holds nothing and
+    no point of the split can be skipped.
+
+    The bounds mean something only for the labels they were written for, so
+    they follow ``g``: a bounded assign rewrites ``gap`` for ITS labels, clears
+    ``ref`` and leaves the centroids in ``pending``; whatever advances ``g``
+    calls ``labels_advanced``, which makes ``pending`` the new ``ref`` only if
+    ``g`` went to exactly those labels and otherwise drops the bounds."""
+    __slots__ = ("g", "S0", "N0", "event", "stream", "data_ptr", "n", "gap", "ref", "pending")
 
     def __init__(self, g, S0, N0, data_ptr, n):
         self.g, self.S0, self.N0 = g, S0, N0
+        self.gap = self.ref = self.pending = None
         self.event = None
         self.stream = None
         self.data_ptr, self.n = data_ptr, n
+
+    def labels_advanced(self, bounded: bool = False) -> None:
+        """``g`` now holds other labels.  ``bounded``: the ones the last
+        bounded assign over this baseline wrote ``gap`` for."""
+        self.ref = self.pending if bounded else None
+        self.pending = None
 
 
 def delta_workspace_bytes(total: int, ntasks: int, k: int) -> int:
@@ -739,6 +865,8 @@ def map_batch_delta(splits: list, img: CentroidImage, sums: torch.Tensor, counts
     if workspace.numel() < need:
         raise ValueError("workspace too small")
     ptrs, ns, gs, s0, n0 = _delta_args(splits, bases, stream)
+    for b in bases:
+        b.labels_advanced()           # exact mode's bounds, if any, were for other labels
     rc = _lib.load().hbmr_kmeans_map_batch_delta(
         B, ptrs, ns, img.dp, _ptr(img.cbf), _ptr(img.chalf), img.k_pad, img.k, _ptr(labels),
         _ptr(workspace), workspace.numel(), _ptr(sums), _ptr(counts), img.fx_shift, gs, s0, n0,
@@ -748,12 +876,19 @@ def map_batch_delta(splits: list, img: CentroidImage, sums: torch.Tensor, counts
 
 def delta_combine(xs: list, labels: torch.Tensor, k: int, sums: torch.Tensor,
                   counts: torch.Tensor, workspace: torch.Tensor, bases: list,
-                  fx_shift: int = FX_SHIFT, stream=None) -> None:
+                  fx_shift: int = FX_SHIFT, stream=None, keep_bounds: bool = False) -> None:
     """The delta combiner alone over precomputed labels (concatenated in task
-    order): rows are bf16 or fp32 (exact mode) ``[n_t, dp]``."""
+    order): rows are bf16 or fp32 (exact mode) ``[n_t, dp]``.  Every
+    ``bases[t]`` advances to ``labels``, and loses its per-point bounds unless
+    ``keep_bounds``: ``labels`` are then what a bounded ``assign_exact_batch``
+    over the same baselines just wrote, and its bounds take effect."""
     B = len(xs)
     if B == 0:
         return
+    # g is rewritten below: the bounds fall unless all of it succeeds
+    pend = [b.pending for b in bases]
+    for b in bases:
+        b.labels_advanced()
     dp = xs[0].shape[1]
     f32 = xs[0].dtype == torch.float32
     for x, b in zip(xs, bases):
@@ -771,6 +906,9 @@ def delta_combine(xs: list, labels: torch.Tensor, k: int, sums: torch.Tensor,
         B, ptrs, ns, dp, int(f32), k, _ptr(labels), _ptr(workspace), workspace.numel(),
         _ptr(sums), _ptr(counts), fx_shift, gs, s0, n0, _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_kmeans_delta_combine")
+    if keep_bounds:
+        for b, p in zip(bases, pend):
+            b.ref = p
 
 
 def map_split_gpu(points, img: CentroidImage, sums, counts, labels=None, stream=None):

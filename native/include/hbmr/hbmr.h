@@ -64,6 +64,20 @@ int hbmr_kmeans_assign_top3_q1_grouped(int nsplit, const void* const* X, const l
                                        int d, int k, const float* cnorm, const float* cmax,
                                        const float* cerr, const float* cerrmax, void* ws,
                                        long ws_bytes, const float* dcc, hipStream_t st);
+/* the grouped call for splits that keep per-point bounds: a point whose stored
+   bound outlasts the centroids' shift since `ref` keeps its label unassigned */
+long hbmr_kmeans_bound_workspace_bytes(long total, int nsplit, int k);
+int hbmr_kmeans_assign_top3_q1_bounded(int nsplit, const void* const* X, const long* n, int dp,
+                                       int f16, const void* Ct, const float* chalf, int k_pad,
+                                       int32_t* labels, const float* const* xnorm,
+                                       const float* const* xbn2, const float* const* xerr,
+                                       int d, int k, const float* cnorm, const float* cmax,
+                                       const float* cerr, const float* cerrmax, void* ws,
+                                       long ws_bytes, const float* dcc,
+                                       const int32_t* const* g, float* const* gap,
+                                       const float* const* ref, const float* cen, void* bws,
+                                       long bws_bytes, unsigned long long* skipped,
+                                       hipStream_t st);
 int hbmr_kmeans_assign_top3_grouped(int nsplit, const void* const* X, const long* n, int dp,
                                     int f16, const void* C, const float* chalf, int k_pad,
                                     int32_t* labels, int32_t* cand, float* scores, float* margin,

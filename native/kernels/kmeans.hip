@@ -2444,11 +2444,23 @@ __device__ __forceinline__ uint32_t lane_rank(unsigned long long m) {
 // Step 1's certification of one point (its kernel top-3 in e, best - second
 // margin m2, cnb / ceb = |c_b|, |c_b - c~_b|): true = not certified, the point
 // goes to step 2.  Shared by the step-1 scan and the fused top-3 epilogue.
-__device__ __forceinline__ bool q1_flagged(const ExactQ1& e, float m2, float cnb, float ceb, int k,
+//
+// GAP: also the point's bound for the next passes (see kmeans_bound_sweep_kernel),
+// a lower bound of min_{j != b} |x - c_j| - |x - c_b| over the fp32 data
+// (distances, not squared), 0 for a flagged point.  The rule that certified
+// the point established D_j - D_b >= delta for every j != b: the generic rule
+// s_b >= s~_b - E_b and s_j <= s~_s + E_max(s), i.e. delta = 2 (mm - eb - es);
+// the pair rule the smaller of its s term 2 (mm - ep) and its t term
+// 2 (m3 - eb - et).  With sqrt(D_b) <= R = sqrt(dhi_b) + a_b (exact_bound's
+// upper bound of D~_b and the operands' rounding error) and sqrt(D + delta) -
+// sqrt(D) falling in D:  |x - c_j| - |x - c_b| >= delta / (sqrt(R^2 + delta) + R),
+// evaluated in fp64, shaved by 2^-30 twice for its own rounding, rounded down.
+template <bool GAP>
+__device__ __forceinline__ bool q1_certify(const ExactQ1& e, float m2, float cnb, float ceb, int k,
                                            double gam, double cm, double cem, double pack_rel,
                                            const float* __restrict__ cnorm,
                                            const float* __restrict__ cerr,
-                                           const float* __restrict__ dcc) {
+                                           const float* __restrict__ dcc, float& gap) {
   const double inflate = 1.0 + 0x1p-20;
   const double xn = ((double)e.xn + (double)e.xe) * inflate;
   const double x2 = (double)e.x2;
@@ -2460,6 +2472,10 @@ __device__ __forceinline__ bool q1_flagged(const ExactQ1& e, float m2, float cnb
               ((double)e.xe + (double)ceb) * inflate, gam, pack_rel, eb, dl_b);
   exact_bound(sb - mm, cm, xn, x2, amax, gam, pack_rel, es, dl_s);
   bool flag = !(mm > eb + es && dl_s >= 2.0 * amax);
+  // GAP: certified margin, score units (D / 2).  The generic rule's, whether
+  // or not that rule held: it is read only once `flag` is false, and a point
+  // that only the pair rule certifies replaces it below.
+  double marg = mm - (eb + es);
   const int b = e.b, sc = e.s, t = e.t;
   if (flag && dcc != nullptr && t < k && t != b) {
     // Pair rule: D_s - D_b >= (D~_s - D~_b) - 2|c~_b - c~_s| e_x
@@ -2483,9 +2499,34 @@ __device__ __forceinline__ bool q1_flagged(const ExactQ1& e, float m2, float cnb
     double et, dl_t;
     const double m3 = e.m3;
     exact_bound(sb - m3, cm, xn, x2, amax, gam, pack_rel, et, dl_t);
-    if (mm > ep && m3 > eb + et && dl_t >= 2.0 * amax) flag = false;
+    if (mm > ep && m3 > eb + et && dl_t >= 2.0 * amax) {
+      flag = false;
+      if constexpr (GAP) marg = fmin(mm - ep, m3 - (eb + et));
+    }
+  }
+  if constexpr (GAP) {
+    gap = 0.f;
+    if (!flag && marg > 0.0) {
+      const double ctb = ((double)cnb + (double)ceb) * inflate;
+      const double eacc = gam * (xn * ctb + 0.5 * ctb * ctb);
+      const double slack = 2.0 * (eacc + fabs(sb) * pack_rel) + x2 * 0x1p-22;
+      const double r = sqrt(fmax(0.0, x2 - 2.0 * sb) + slack) * (1.0 + 0x1p-40) +
+                       ((double)e.xe + (double)ceb) * inflate;
+      const double delta = 2.0 * marg * (1.0 - 0x1p-30);
+      const double g = delta / (sqrt(r * r + delta) * (1.0 + 0x1p-40) + r) * (1.0 - 0x1p-30);
+      gap = fmaxf(0.f, __double2float_rd(g));
+    }
   }
   return flag;
+}
+
+__device__ __forceinline__ bool q1_flagged(const ExactQ1& e, float m2, float cnb, float ceb, int k,
+                                           double gam, double cm, double cem, double pack_rel,
+                                           const float* __restrict__ cnorm,
+                                           const float* __restrict__ cerr,
+                                           const float* __restrict__ dcc) {
+  float unused;
+  return q1_certify<false>(e, m2, cnb, ceb, k, gam, cm, cem, pack_rel, cnorm, cerr, dcc, unused);
 }
 
 // Step 1 over one block of 256 * kQ1Per points of split sidx (block index blk
@@ -2634,8 +2675,12 @@ struct FusedQ1Fin {
   ExactQ1* q1;
   long cap1;
   unsigned long long* stats;
+  // the bounded pass (BND): entry p of the split's list is point row idx[p]
+  // (n = the list's length); a certified point's bound goes to gap[row]
+  const uint32_t* idx;
+  float* gap;
 
-  template <class AM, int PB>
+  template <class AM, int PB, bool BND = false>
   __device__ __forceinline__ void operator()(const AM (&am)[PB], int h, long p0, int col, long n,
                                              int32_t* __restrict__ labels) const {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2673,23 +2718,32 @@ struct FusedQ1Fin {
       const long p = p0 + pb * 32 + col;
       flag[pb] = false;
       if (h == 0 && p < n) {
-        labels[p] = c[0];
+        long row = p;
+        if constexpr (BND) row = idx[p];
+        labels[row] = c[0];
         const float bs = am[pb].score(v[0]);
         const float m2 = bs - am[pb].score(v[1]);
         ExactQ1& q = e[pb];
-        q.row = (uint32_t)p;
+        q.row = (uint32_t)row;
         q.split = (uint32_t)sidx;
         q.b = c[0];
         q.s = c[1];
         q.t = c[2];
         q.sb = bs;
         q.m3 = bs - am[pb].score(v[2]);
-        q.x2 = xbn2[p];
-        q.xn = xnorm[p];
-        q.xe = xerr[p];
+        q.x2 = xbn2[row];
+        q.xn = xnorm[row];
+        q.xe = xerr[row];
         q.pad0 = q.pad1 = 0.f;
-        flag[pb] = q.s < k && q1_flagged(q, m2, cnorm[q.b], cerr[q.b], k, gam, cm, cem,
-                                         pack_rel, cnorm, cerr, dcc);
+        if constexpr (BND) {
+          float gp = 0.f;     // fewer than two clusters: no bound
+          flag[pb] = q.s < k && q1_certify<true>(q, m2, cnorm[q.b], cerr[q.b], k, gam, cm, cem,
+                                                 pack_rel, cnorm, cerr, dcc, gp);
+          gap[row] = gp;
+        } else {
+          flag[pb] = q.s < k && q1_flagged(q, m2, cnorm[q.b], cerr[q.b], k, gam, cm, cem,
+                                           pack_rel, cnorm, cerr, dcc);
+        }
       }
       const unsigned long long m = __ballot(flag[pb]);
       rank[pb] = lane_rank(m);
@@ -2786,7 +2840,9 @@ __device__ __forceinline__ void top2_insert(PackedTop2x8& am, const f32x16& acc,
   }
 }
 
-template <int D, bool F16>
+// BND (the bounded pass): entry p of the workgroup is point row fin.idx[p], n
+// the length of the split's list
+template <int D, bool F16, bool BND = false>
 __device__ __forceinline__ void assign_tile_v3(const __bf16* __restrict__ X, long n,
                                                const __bf16* __restrict__ Ct,
                                                const float* __restrict__ chalf, int ntiles,
@@ -2831,6 +2887,7 @@ __device__ __forceinline__ void assign_tile_v3(const __bf16* __restrict__ X, lon
   for (int pb = 0; pb < PB; ++pb) {
     long p = p0 + pb * 32 + col;
     if (p >= n) p = n - 1;
+    if constexpr (BND) p = fin.idx[p];
     const uint4* row = reinterpret_cast<const uint4*>(X + p * D);
 #pragma unroll
     for (int s = 0; s < KS; ++s) bfrag[pb][s] = __builtin_bit_cast(bf16x8, row[2 * s + h]);
@@ -2881,7 +2938,7 @@ __device__ __forceinline__ void assign_tile_v3(const __bf16* __restrict__ X, lon
     for (int pb = 0; pb < PB; ++pb) top2_insert(am[pb], acc[pb], code, vmask);
     bias(nbuf, bz);
   }
-  fin(am, h, p0, col, n, labels);
+  fin.template operator()<PackedTop2x8, PB, BND>(am, h, p0, col, n, labels);
 }
 
 struct TopQ1Table {       // the batch's splits, by value (X, per-point norms)
@@ -2938,6 +2995,173 @@ __global__ __launch_bounds__(256, HBMR_EXACT_MINB) void kmeans_assign_top3_q1_v3
   fin.sidx = s;
   assign_tile_v3<D, F16>(tbl.X[s], tbl.off[s + 1] - o, Ct, chalf, ntiles, labels + o,
                          b - tbl.blk[s], smem, fin);
+}
+
+// ---------------------------------------------------------------------------
+// The bounded pass (hbmr_kmeans_assign_top3_q1_bounded).  A split's reference
+// partition keeps, beside its labels g, a certified lower bound gap[p] of
+// min_{j != g(p)} |x_p - c_j| - |x_p - c_g(p)| (distances over the fp32 data)
+// against the centroids `ref`.  For centroids c' the triangle inequality gives
+//   |x - c'_g| <= |x - ref_g| + shift[g],  |x - c'_j| >= |x - ref_j| - shift[j],
+// shift[j] = |c'_j - ref_j|, so the bound against c' is at least
+// gap - shift[g] - max_j shift[j]; where that stays > 0 the exact arg-min is
+// still g (uniquely) and the point needs no distance at all (Hamerly's test).
+//   shift : shift[j] per distinct ref of the batch, fp64, rounded up;
+//   sweep : decays every gap, keeps the label of a point whose bound holds and
+//           lists the other rows per split (device-side counts);
+//   assign: the v3 fused assign over the lists (row indirection), whose
+//           epilogue leaves a fresh gap for the points it certifies.
+constexpr int kSweepPer = 8;                         // points per thread in the sweep
+constexpr int kBoundHdr = 512;                       // list counts | max shifts (u32 / f32 [64])
+
+struct ShiftTable {
+  const float* ref[kMaxGroup];
+};
+
+// shift[r][j] = |cen_j - ref[r]_j| (>=), smax[r] = max_j (as bits: floats >= 0)
+__global__ __launch_bounds__(64) void kmeans_bound_shift_kernel(
+    const ShiftTable tbl, const float* __restrict__ cen, int k, int d, float* __restrict__ shift,
+    uint32_t* __restrict__ smax) {
+  const int j = blockIdx.x, r = blockIdx.y;
+  const float* a = cen + (size_t)j * d;
+  const float* b = tbl.ref[r] + (size_t)j * d;
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < d; i += 64) {
+    const double e = (double)a[i] - (double)b[i];
+    acc = fma(e, e, acc);
+  }
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
+  if (threadIdx.x == 0) {
+    const float s = __double2float_ru(sqrt(acc) * (1.0 + 0x1p-40));
+    shift[(size_t)r * k + j] = s;
+    atomicMax(smax + r, __float_as_uint(s));
+  }
+}
+
+// a - b rounded toward -inf where that is positive (else some value <= 0), for
+// b >= 0: the rounding error of the fp32 difference is itself an fp32 number
+// (Knuth's two-sum); results too small for it to be one count as 0
+__device__ __forceinline__ float sub_rd_pos(float a, float b) {
+  const float t = a - b;
+  if (!(t > 0x1p-100f)) return 0.f;
+  const float bb = t - a;
+  const float err = (a - (t - bb)) - (b + bb);
+  return err < 0.f ? __uint_as_float(__float_as_uint(t) - 1u) : t;
+}
+
+struct SweepTable {
+  int nsplit;
+  const int32_t* g[kMaxGroup];     // the reference partition's labels
+  float* gap[kMaxGroup];           // its bounds (null: none yet, every row is listed)
+  int rid[kMaxGroup];              // which shift row the gaps refer to
+  long n[kMaxGroup];
+  long off[kMaxGroup];
+  long blk[kMaxGroup + 1];
+};
+
+__global__ __launch_bounds__(256) void kmeans_bound_sweep_kernel(
+    const SweepTable tbl, int k, const float* __restrict__ shift,
+    const float* __restrict__ smax, int32_t* __restrict__ labels, uint32_t* __restrict__ cnt,
+    uint32_t* __restrict__ idx) {
+  const long b = blockIdx.x;
+  int lo = 0, hi = tbl.nsplit;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tbl.blk[mid] <= b) lo = mid; else hi = mid;
+  }
+  const int s = __builtin_amdgcn_readfirstlane(lo);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long n = tbl.n[s], o = tbl.off[s];
+  const int32_t* __restrict__ g = tbl.g[s];
+  float* __restrict__ gap = tbl.gap[s];
+  const float* __restrict__ sh = shift + (size_t)tbl.rid[s] * k;
+  const float sm = gap ? smax[tbl.rid[s]] : 0.f;
+  const long p0 = (b - tbl.blk[s]) * (256 * kSweepPer);
+  __shared__ uint32_t wcnt[4][kSweepPer];
+  __shared__ uint32_t base_s;
+  bool list[kSweepPer];
+  uint32_t rank[kSweepPer];
+#pragma unroll
+  for (int i = 0; i < kSweepPer; ++i) {
+    const long p = p0 + i * 256 + tid;
+    list[i] = false;
+    if (p < n) {
+      list[i] = true;
+      if (gap) {
+        const int32_t c = g[p];
+        // rounded toward -inf: the stored bound never exceeds the true one
+        const float v =
+            (uint32_t)c < (uint32_t)k ? sub_rd_pos(sub_rd_pos(gap[p], sh[c]), sm) : 0.f;
+        if (v > 0.f) {
+          list[i] = false;
+          labels[o + p] = c;
+          gap[p] = v;
+        }
+      }
+    }
+    const unsigned long long m = __ballot(list[i]);
+    rank[i] = lane_rank(m);
+    if (lane == 0) wcnt[wave][i] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+#pragma unroll
+      for (int i = 0; i < kSweepPer; ++i) {
+        const uint32_t c = wcnt[w][i];
+        wcnt[w][i] = tot;
+        tot += c;
+      }
+    base_s = tot ? atomicAdd(cnt + s, tot) : 0u;
+  }
+  __syncthreads();
+  uint32_t* out = idx + o + base_s;
+#pragma unroll
+  for (int i = 0; i < kSweepPer; ++i)
+    if (list[i]) out[wcnt[wave][i] + rank[i]] = (uint32_t)(p0 + i * 256 + tid);
+}
+
+struct GapTable {
+  float* gap[kMaxGroup];
+};
+
+// The v3 fused assign over each split's list: the grid is the full batch's
+// (the list lengths live on the device); a workgroup past its split's list
+// leaves before it stages anything.
+template <int D, bool F16>
+__global__ __launch_bounds__(256, HBMR_EXACT_MINB) void kmeans_assign_top3_q1_bounded_kernel(
+    const TopQ1Table tbl, const GapTable gt, const __bf16* __restrict__ Ct,
+    const float* __restrict__ chalf, int ntiles, int32_t* __restrict__ labels, FusedQ1Fin fin,
+    const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ idx,
+    unsigned long long* __restrict__ skipped) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  if (blockIdx.x == 0 && threadIdx.x == 0 && skipped != nullptr) {
+    unsigned long long sk = 0;
+    for (int i = 0; i < tbl.nsplit; ++i)
+      sk += (unsigned long long)(tbl.off[i + 1] - tbl.off[i]) - cnt[i];
+    if (sk) atomicAdd(skipped, sk);
+  }
+  const long b = hbmr_xcd_remap(blockIdx.x, gridDim.x);
+  int lo = 0, hi = tbl.nsplit;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tbl.blk[mid] <= b) lo = mid; else hi = mid;
+  }
+  const int s = __builtin_amdgcn_readfirstlane(lo);
+  const long nl = (long)__builtin_amdgcn_readfirstlane(cnt[s]);
+  const long lb = b - tbl.blk[s];
+  if (lb * 256 >= nl) return;
+  const long o = tbl.off[s];
+  fin.xnorm = tbl.xnorm[s];
+  fin.xbn2 = tbl.xbn2[s];
+  fin.xerr = tbl.xerr[s];
+  fin.sidx = s;
+  fin.idx = idx + o;
+  fin.gap = gt.gap[s];
+  assign_tile_v3<D, F16, true>(tbl.X[s], nl, Ct, chalf, ntiles, labels + o, lb, smem, fin);
 }
 
 // 16 features of a row per lane of an 8-lane group: 128m + 32h + 4sub + (0..3)
@@ -3871,6 +4095,128 @@ int hbmr_kmeans_assign_top3_q1_grouped(int nsplit, const void* const* X, const l
   return (int)hipGetLastError();
 }
 
+// workspace of the bounded pass: list counts and max shifts (kBoundHdr), a
+// shift row per split (at most one distinct ref each), the splits' row lists
+long hbmr_kmeans_bound_workspace_bytes(long total, int nsplit, int k) {
+  if (total < 0 || nsplit <= 0 || nsplit > kMaxGroup || k <= 0) return -1;
+  const size_t sh = ((size_t)nsplit * k * sizeof(float) + 255) & ~(size_t)255;
+  return (long)(kBoundHdr + sh + (size_t)total * sizeof(uint32_t));
+}
+
+// hbmr_kmeans_assign_top3_q1_grouped for splits that keep per-point bounds
+// (see kmeans_bound_shift_kernel): g[i] the split's reference labels, gap[i]
+// its bounds [n_i] against the centroids ref[i] ([k, d] fp32; null: gap[i]
+// holds nothing yet and every row is assigned), cen the current centroids
+// [k, d].  Leaves what the grouped call leaves (labels of every point, the
+// step-2 queue and flagged count in ws), gap[i] valid against cen, and adds
+// the number of points it did not assign to *skipped (device, may be null).
+// The list lengths stay on the device: no synchronisation, no read-back.
+// Always the v3 kernel: there is no bounded v2, so a caller that honours the
+// v2 selection (hbmr_kmeans_get_exact_kernel() == 2) uses the grouped call.
+int hbmr_kmeans_assign_top3_q1_bounded(int nsplit, const void* const* X, const long* n, int dp,
+                                       int f16, const void* Ct, const float* chalf, int k_pad,
+                                       int32_t* labels, const float* const* xnorm,
+                                       const float* const* xbn2, const float* const* xerr,
+                                       int d, int k, const float* cnorm, const float* cmax,
+                                       const float* cerr, const float* cerrmax, void* ws,
+                                       long ws_bytes, const float* dcc,
+                                       const int32_t* const* g, float* const* gap,
+                                       const float* const* ref, const float* cen, void* bws,
+                                       long bws_bytes, unsigned long long* skipped,
+                                       hipStream_t st) {
+  if (nsplit <= 0 || nsplit > kMaxGroup || k_pad % 32 || k <= 0 || k_pad < k || d <= 0 ||
+      d > kRefineMaxDp || !labels || ((uintptr_t)ws & 255) || (dp != 64 && dp != 128) || !Ct ||
+      !g || !gap || !ref || !cen || !bws || ((uintptr_t)bws & 255))
+    return (int)hipErrorInvalidValue;
+  TopQ1Table t;
+  SweepTable sw;
+  GapTable gt;
+  ShiftTable sh;
+  memset(&t, 0, sizeof(t));
+  memset(&sw, 0, sizeof(sw));
+  memset(&gt, 0, sizeof(gt));
+  memset(&sh, 0, sizeof(sh));
+  t.nsplit = sw.nsplit = nsplit;
+  constexpr int pts = 4 * 2 * 32;             // AssignV2<D>::WAVES * PB * 32
+  long total = 0, nb = 0, nsb = 0;
+  int nref = 0;
+  for (int i = 0; i < nsplit; ++i) {
+    if (n[i] < 0 || n[i] > 0x7fffffffL || !gap[i] || (ref[i] && !g[i]))
+      return (int)hipErrorInvalidValue;
+    t.X[i] = reinterpret_cast<const __bf16*>(X[i]);
+    t.xnorm[i] = xnorm[i];
+    t.xbn2[i] = xbn2[i];
+    t.xerr[i] = xerr[i];
+    t.off[i] = sw.off[i] = total;
+    t.blk[i] = nb;
+    sw.blk[i] = nsb;
+    sw.n[i] = n[i];
+    sw.g[i] = g[i];
+    gt.gap[i] = gap[i];
+    if (ref[i]) {
+      int r = 0;
+      while (r < nref && sh.ref[r] != ref[i]) ++r;
+      if (r == nref) sh.ref[nref++] = ref[i];
+      sw.rid[i] = r;
+      sw.gap[i] = gap[i];
+    }
+    total += n[i];
+    nb += ceil_div(n[i], pts);
+    nsb += ceil_div(n[i], 256 * kSweepPer);
+  }
+  t.off[nsplit] = total;
+  t.blk[nsplit] = nb;
+  sw.blk[nsplit] = nsb;
+  const RefineLayout Ly = refine_layout(nsplit, n);
+  if (ws_bytes < (long)Ly.bytes ||
+      bws_bytes < hbmr_kmeans_bound_workspace_bytes(total, nsplit, k))
+    return (int)hipErrorInvalidValue;
+  char* w = static_cast<char*>(ws);
+  char* bw = static_cast<char*>(bws);
+  HBMR_RETURN_IF_ERROR(hipMemsetAsync(w, 0, kHdrClear, st));
+  if (nb == 0) return 0;
+  if (nb > 0x7fffffffL) return (int)hipErrorInvalidValue;
+  HBMR_RETURN_IF_ERROR(hipMemsetAsync(bw, 0, kBoundHdr, st));
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(bw);
+  uint32_t* smax = cnt + kMaxGroup;
+  float* shift = reinterpret_cast<float*>(bw + kBoundHdr);
+  uint32_t* idx = reinterpret_cast<uint32_t*>(
+      bw + kBoundHdr + (((size_t)nsplit * k * sizeof(float) + 255) & ~(size_t)255));
+  if (nref > 0) {
+    hipLaunchKernelGGL(kmeans_bound_shift_kernel, dim3((unsigned)k, (unsigned)nref), dim3(64), 0,
+                       st, sh, cen, k, d, shift, smax);
+    HBMR_RETURN_IF_ERROR(hipGetLastError());
+  }
+  hipLaunchKernelGGL(kmeans_bound_sweep_kernel, dim3((unsigned)nsb), dim3(256), 0, st, sw, k,
+                     shift, reinterpret_cast<const float*>(smax), labels, cnt, idx);
+  HBMR_RETURN_IF_ERROR(hipGetLastError());
+  int tb = 0;
+  while ((1 << tb) < k_pad / 32) ++tb;
+  FusedQ1Fin fin;
+  memset(&fin, 0, sizeof(fin));
+  fin.k = k;
+  fin.gam = (double)(d + 2) * 0x1p-23 * 1.01;
+  fin.pack_rel = ldexp(1.0, 4 + tb - 23);
+  fin.cnorm = cnorm;
+  fin.cerr = cerr;
+  fin.dcc = dcc;
+  fin.qcount = reinterpret_cast<uint32_t*>(w);
+  fin.q1 = reinterpret_cast<ExactQ1*>(w + Ly.off1);
+  fin.cap1 = Ly.cap1;
+  fin.stats = reinterpret_cast<unsigned long long*>(w + kStatsOff);
+  fin.cmax_p = cmax;
+  fin.cerrmax_p = cerrmax;
+  auto kern = dp == 64 ? (f16 ? kmeans_assign_top3_q1_bounded_kernel<64, true>
+                              : kmeans_assign_top3_q1_bounded_kernel<64, false>)
+                       : (f16 ? kmeans_assign_top3_q1_bounded_kernel<128, true>
+                              : kmeans_assign_top3_q1_bounded_kernel<128, false>);
+  const size_t lds = dp == 64 ? AssignV2<64>::LDS_BYTES : AssignV2<128>::LDS_BYTES;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(256), lds, st, t, gt,
+                     reinterpret_cast<const __bf16*>(Ct), chalf, k_pad / 32, labels, fin,
+                     (const uint32_t*)cnt, (const uint32_t*)idx, skipped);
+  return (int)hipGetLastError();
+}
+
 int hbmr_kmeans_refine_f32(const float* X32, long n, int d, int ldx, const float* xnorm,
                            const float* xbn2, const float* xerr, const float* C32, int k,
                            int k_pad, const float* cnorm, const float* cmax, const float* cerr,
@@ -3923,6 +4269,9 @@ int hbmr_kmeans_set_exact_kernel(int v) {
   g_exact_kernel = v == 2 || v == 3 ? v : -1;
   return old;
 }
+
+// the fused exact top-3 kernel in effect: 3 or 2
+int hbmr_kmeans_get_exact_kernel(void) { return exact_kernel(); }
 
 int hbmr_kmeans_image16_tiled(const void* c16, int k_pad, int dp, void* c16t, hipStream_t st) {
   if (k_pad <= 0 || k_pad % 32 || (dp != 64 && dp != 128) || !c16 || !c16t)
