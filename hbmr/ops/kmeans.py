@@ -371,6 +371,14 @@ REFINE_VERSION = int(os.environ.get("HBMR_REFINE", "3"))
 MAX_REFINE_BATCH = 64     # splits per refine v3 batch (the kernels' split table)
 
 
+def _check_refine_dim(img: "CentroidImage") -> None:
+    """Refine v3 reads the fp32 centroid rows ([k, d], row stride d) as 16-byte
+    vectors (hbmr_kmeans_refine_batch_finish): refused here, before anything is
+    launched.  HBMR_REFINE=2 falls back to the scalar-load v1 kernel."""
+    if REFINE_VERSION >= 3 and img.d % 8:
+        raise ValueError(f"refine v3 needs d % 8 == 0 (d = {img.d}): HBMR_REFINE=2 takes any d")
+
+
 def _refine_ws(ns: list, device, scratch: dict | None):
     """Queue workspace of a refine v3 batch, kept in ``scratch`` across calls
     (one stream orders the reuse)."""
@@ -392,6 +400,7 @@ class _RefineBatch:
     once (step 2 + Elkan scan over the batch's queues)."""
 
     def __init__(self, splits: list, img: "CentroidImage", stats, scratch, stream):
+        _check_refine_dim(img)
         self.splits, self.img, self.stats, self.stream = splits, img, stats, stream
         self.dt = splits[0].xb.dtype
         self.ns, self.ws = _refine_ws([sp.shape[0] for sp in splits], splits[0].x32.device,
@@ -463,6 +472,7 @@ def assign_exact(split: ExactSplit, img: CentroidImage, stats: torch.Tensor,
                  scratch: dict | None = None, stream=None) -> torch.Tensor:
     """Exact labels of the split's fp32 points: top-3 bf16 assign +
     certification / fp64 re-score.  Returns labels [n] (a scratch view)."""
+    _check_refine_dim(img)
     n = split.shape[0]
     dev = split.xb.device
     scratch = {} if scratch is None else scratch
@@ -511,6 +521,7 @@ def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, ou
     ``skipped`` (int64 [1], device) += the points not assigned."""
     if not splits:
         return
+    _check_refine_dim(img)
     if bounds is not None and (len(bounds) != len(splits) or not bounds_supported(img)):
         raise ValueError("bounds: one baseline per split, grouped fused v3 assign (dp <= 128)")
     dev = splits[0].xb.device

@@ -4141,7 +4141,8 @@ int hbmr_kmeans_assign_top3_q1_bounded(int nsplit, const void* const* X, const l
   long total = 0, nb = 0, nsb = 0;
   int nref = 0;
   for (int i = 0; i < nsplit; ++i) {
-    if (n[i] < 0 || n[i] > 0x7fffffffL || !gap[i] || (ref[i] && !g[i]))
+    // (an empty split has no rows to bound: its g / gap may be null)
+    if (n[i] < 0 || n[i] > 0x7fffffffL || (n[i] > 0 && (!gap[i] || (ref[i] && !g[i]))))
       return (int)hipErrorInvalidValue;
     t.X[i] = reinterpret_cast<const __bf16*>(X[i]);
     t.xnorm[i] = xnorm[i];
