@@ -374,7 +374,9 @@ MAX_REFINE_BATCH = 64     # splits per refine v3 batch (the kernels' split table
 def _check_refine_dim(img: "CentroidImage") -> None:
     """Refine v3 reads the fp32 centroid rows ([k, d], row stride d) as 16-byte
     vectors (hbmr_kmeans_refine_batch_finish): refused here, before anything is
-    launched.  HBMR_REFINE=2 falls back to the scalar-load v1 kernel."""
+    launched.  HBMR_REFINE=1 or 2 selects the single-kernel form, which takes
+    any d (it falls back to its scalar-load kernel where rows are not whole
+    16-byte vectors)."""
     if REFINE_VERSION >= 3 and img.d % 8:
         raise ValueError(f"refine v3 needs d % 8 == 0 (d = {img.d}): HBMR_REFINE=2 takes any d")
 
@@ -442,8 +444,10 @@ class _RefineBatch:
 def refine_f32(split: ExactSplit, img: CentroidImage, labels, cand, scores, margin,
                stats: torch.Tensor, stream=None, scratch: dict | None = None) -> None:
     """Certify the MFMA labels against the fp32 data; re-score the uncertain
-    points in fp64 (refine v3, the queue pipeline; HBMR_REFINE=1/2: the older
-    single-kernel forms).  stats (int64 [3]) += (flagged, relabelled, points
+    points in fp64 (refine v3, the queue pipeline; HBMR_REFINE=1 and 2 both mean
+    the older single-kernel form, hbmr_kmeans_refine_f32, which picks its
+    vector-load or scalar-load kernel by d and alignment).  stats (int64 [3]) +=
+    (flagged, relabelled, points
     that needed the neighbour scan); a [5] stats also counts the scan's
     neighbour distances and its full scans."""
     n = split.shape[0]

@@ -158,74 +158,34 @@ __device__ __forceinline__ float vmed3(float a, float b, float c) {
   return r;
 }
 
-// Packed running TOP-3 (exact mode, hbmr.kmeans.exact): same (tile, register)
-// codes as PackedArgMax, but each of two register-parity tracks keeps its best
-// three b >= s >= t.  Inserting u: t = med3(s, t, u), s = med3(b, s, u),
-// b = max(b, u) (the middle of a sorted pair and u is the new lower member) —
-// 3 VALU ops per score instead of 0.5, two independent chains per 32 points.
-struct PackedTop3 : PackedArgMax {
-  float s0, s1, t0, t1;
-  __device__ __forceinline__ void init(int ntiles) {
-    PackedArgMax::init(ntiles);
-    s0 = s1 = t0 = t1 = -3.0e38f;
-  }
-  __device__ __forceinline__ static void insert(float& b, float& s, float& t, float u) {
-    t = vmed3(s, t, u);
-    s = vmed3(b, s, u);
-    b = vmax3(b, u, u);
-  }
-  __device__ __forceinline__ void update(const f32x16& acc, int tt) {
-    const uint32_t base = top - ((uint32_t)tt << 4);
-    uint32_t code[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      code[r] = base | (15u - r);
-      asm("" : "+s"(code[r]));
-    }
-#pragma unroll
-    for (int r = 0; r < 16; r += 2) {
-      const float u0 = __uint_as_float((__float_as_uint(acc[r + 0]) & vmask) | code[r + 0]);
-      const float u1 = __uint_as_float((__float_as_uint(acc[r + 1]) & vmask) | code[r + 1]);
-      insert(b0, s0, t0, u0);
-      insert(b1, s1, t1, u1);
-    }
-  }
-  __device__ __forceinline__ void top3(float& b, float& s, float& t) const {
-    b = b0; s = s0; t = t0;
-    insert(b, s, t, b1);
-    insert(b, s, t, s1);
-    insert(b, s, t, t1);
-  }
-};
+// Insert packed score u into the sorted triple b >= s >= t: t = med3(s, t, u),
+// s = med3(b, s, u), b = max(b, u) (the middle of a sorted pair and u is the
+// new lower member).
+__device__ __forceinline__ void packed_insert3(float& b, float& s, float& t, float u) {
+  t = vmed3(s, t, u);
+  s = vmed3(b, s, u);
+  b = vmax3(b, u, u);
+}
 
-// Packed running TOP-2 per TRACK (exact mode default): the 16 accumulator
-// registers of a lane form 8 tracks (register r -> track r & 7), each keeping
-// its best two: s = med3(b, s, u), b = max(b, u) — 2 VALU ops per score (+ the
-// and_or that packs the code) instead of PackedTop3's 3.  With K = 128 one
-// 32x32 output tile is 8 MFMAs (256 MFMA cycles per SIMD, 64 of them blocking
-// vector issue): the top-3 epilogue's 4 issue slots per score did not fit the
-// remaining 192 cycles (top-3 assign ran 20 % behind the plain arg-max), 3 do.
-// Together with the lane half h, a cluster's track is its index bits 0-2 (4
-// tracks, r & 3) or 0-3 (8 tracks, r & 7): cluster = tile*32 + (r&3) +
-// 8(r>>2) + 4h.  The top 3 of a point are the
-// top 3 of the 32 track candidates; every cluster that is not a candidate
+// Packed running TOP-2 per TRACK (exact mode, hbmr.kmeans.exact): same (tile,
+// register) codes as PackedArgMax.  The 16 accumulator registers of a lane
+// form NT = 4 tracks (register r -> track r & 3), each keeping its best two.
+// A full running top-3 (3 VALU ops per score) did not fit beside the MFMAs:
+// with K = 128 one 32x32 output tile is 8 MFMAs (256 MFMA cycles per SIMD, 64
+// of them blocking vector issue), and its 4 issue slots per score overran the
+// remaining 192 cycles (top-3 assign ran 20 % behind the plain arg-max).
+// Together with the lane half h, a cluster's track is its index bits 0-2:
+// cluster = tile*32 + (r&3) + 8(r>>2) + 4h.  The top 3 of a point are the
+// top 3 of the 16 track candidates; every cluster that is not a candidate
 // scores <= its track's second, which is <= the third — unless the best and
 // the second share a track, which finish_point flags (t = b, margin 0: step 2
 // of the certification then defers the point to the neighbour scan).
 // workgroups per CU the exact (top-3) assign kernels are built for: 3 keeps
 // them at <= 168 VGPRs, i.e. 3 waves per SIMD like the plain arg-max kernel
-#ifndef HBMR_EXACT_MINB
-#define HBMR_EXACT_MINB 3
-#endif
-#ifndef HBMR_EXACT_TRACKS
-#define HBMR_EXACT_TRACKS 4   // register tracks per lane (4: r & 3; 8: r & 7)
-#endif
-#ifndef HBMR_EXACT_PAIRINS
-#define HBMR_EXACT_PAIRINS 1  // insert a track's two scores of a tile at once
-#endif
+constexpr int kExactMinB = 3;
 struct PackedTop2x8 : PackedArgMax {
-  static constexpr int NT = HBMR_EXACT_TRACKS;
-  static constexpr uint32_t TMASK = NT == 8 ? 15u : 7u;   // cluster bits of a track
+  static constexpr int NT = 4;             // register tracks per lane (r & 3)
+  static constexpr uint32_t TMASK = 7u;    // cluster bits of a track
   float tb[NT], ts[NT];
   __device__ __forceinline__ void init(int ntiles) {
     PackedArgMax::init(ntiles);
@@ -240,7 +200,6 @@ struct PackedTop2x8 : PackedArgMax {
       code[r] = base | (15u - r);
       asm("" : "+s"(code[r]));
     }
-#if HBMR_EXACT_PAIRINS
     // registers r and r + NT belong to one track: both are inserted at once —
     // the second of {b >= s, u, v} is max(med3(b, u, v), s) — 3 VALU ops per
     // two scores instead of 4 (the epilogue is what bounds this kernel)
@@ -253,38 +212,19 @@ struct PackedTop2x8 : PackedArgMax {
       ts[r % NT] = vmax3(m, ts[r % NT], ts[r % NT]);
       tb[r % NT] = vmax3(tb[r % NT], u, v);
     }
-#else
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float u = __uint_as_float((__float_as_uint(acc[r]) & vmask) | code[r]);
-      ts[r % NT] = vmed3(tb[r % NT], ts[r % NT], u);
-      tb[r % NT] = vmax3(tb[r % NT], u, u);
-    }
-#endif
   }
   __device__ __forceinline__ void top3(float& b, float& s, float& t) const {
     b = s = t = -3.0e38f;
 #pragma unroll
     for (int i = 0; i < NT; ++i) {
-      PackedTop3::insert(b, s, t, tb[i]);
-      PackedTop3::insert(b, s, t, ts[i]);
+      packed_insert3(b, s, t, tb[i]);
+      packed_insert3(b, s, t, ts[i]);
     }
   }
-  static constexpr bool kTracks = true;
 };
 
-template <class AM, class = void> struct HasTracks { static constexpr bool value = false; };
-template <class AM> struct HasTracks<AM, std::void_t<decltype(AM::kTracks)>> {
-  static constexpr bool value = AM::kTracks;
-};
-
-#ifndef HBMR_EXACT_TOP3
-#define HBMR_EXACT_TOP3 0   // 1: the full running top-3 (PackedTop3)
-#endif
 template <bool EXACT>
-using ArgMaxT = typename std::conditional<
-    EXACT, typename std::conditional<HBMR_EXACT_TOP3 != 0, PackedTop3, PackedTop2x8>::type,
-    PackedArgMax>::type;
+using ArgMaxT = typename std::conditional<EXACT, PackedTop2x8, PackedArgMax>::type;
 
 // (score, cluster) insertion into a sorted triple; ties to the lower cluster
 __device__ __forceinline__ void insert3(float (&v)[3], int (&c)[3], float u, int cu) {
@@ -311,8 +251,7 @@ __device__ __forceinline__ void finish_point(const AM& am, int h, long p, long n
                                              int32_t* __restrict__ labels,
                                              int32_t* __restrict__ cand,
                                              float* __restrict__ scores,
-                                             float* __restrict__ margin,
-                                             uint32_t* __restrict__ hist, long cs = -1) {
+                                             float* __restrict__ margin, long cs = -1) {
   // cs: stride of the second candidate / margin (n for one split; the batch
   // size when a grouped launch writes a batch's arrays)
   if (cs < 0) cs = n;
@@ -325,7 +264,6 @@ __device__ __forceinline__ void finish_point(const AM& am, int h, long p, long n
     if (h == 0 && p < n) {
       labels[p] = cluster;
       if (scores) scores[p] = am.score(bv);
-      if (hist) atomicAdd(hist + cluster, 1u);  // fused histogram for the sorted combiner
     }
   } else {
     float v[3];
@@ -342,12 +280,10 @@ __device__ __forceinline__ void finish_point(const AM& am, int h, long p, long n
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) insert3(v, c, ov[i], oc[i]);
-    if constexpr (HasTracks<AM>::value) {
-      // best and second in one track: the rest is bounded only by the second
-      if (((c[0] ^ c[1]) & AM::TMASK) == 0) {
-        v[2] = v[0];
-        c[2] = c[0];
-      }
+    // best and second in one track: the rest is bounded only by the second
+    if (((c[0] ^ c[1]) & AM::TMASK) == 0) {
+      v[2] = v[0];
+      c[2] = c[0];
     }
     if (h == 0 && p < n) {
       labels[p] = c[0];
@@ -357,19 +293,18 @@ __device__ __forceinline__ void finish_point(const AM& am, int h, long p, long n
       scores[p] = bs;
       margin[p] = bs - am.score(v[1]);
       margin[cs + p] = bs - am.score(v[2]);
-      if (hist) atomicAdd(hist + c[0], 1u);
     }
   }
 }
 
-// One workgroup's tile of points [blk*PTS, (blk+1)*PTS) of one split.
+// v1, the chunked form (launched at D = 256 only; D <= 128 takes v2 below):
+// one workgroup's tile of points [blk*PTS, (blk+1)*PTS) of one split.
 template <int D, bool EXACT = false, bool F16 = false>
 __device__ __forceinline__ void assign_tile(const __bf16* __restrict__ X, long n,
                                             const __bf16* __restrict__ C,
                                             const float* __restrict__ chalf, int nchunks,
                                             int32_t* __restrict__ labels,
-                                            float* __restrict__ scores,
-                                            uint32_t* __restrict__ hist, long blk, char* smem,
+                                            float* __restrict__ scores, long blk, char* smem,
                                             int32_t* __restrict__ cand = nullptr,
                                             float* __restrict__ margin = nullptr) {
   using Cfg = AssignCfg<D>;
@@ -455,7 +390,7 @@ __device__ __forceinline__ void assign_tile(const __bf16* __restrict__ X, long n
 
 #pragma unroll
   for (int pb = 0; pb < PB; ++pb)
-    finish_point<EXACT>(am[pb], h, p0 + pb * 32 + col, n, labels, cand, scores, margin, hist);
+    finish_point<EXACT>(am[pb], h, p0 + pb * 32 + col, n, labels, cand, scores, margin);
 }
 
 // ---------------------------------------------------------------------------
@@ -469,6 +404,12 @@ __device__ __forceinline__ void assign_tile(const __bf16* __restrict__ X, long n
 //   MFMAs + arg-max epilogue of tile t.
 // A DMA thus has NS-1 tiles (≈(NS-1)·512 MFMA cycles) to land: with NS = 2 the
 // L2 latency under full-chip load was exposed every tile.
+// waves per v2 workgroup sharing one centroid stream; 8 (2 per SIMD, half the
+// L2→LDS traffic per FLOP) measured 16–19 % slower than 4 at 100M×1024×128
+// (profiles/kmeans_assign_tuning.md)
+constexpr int kV2Waves = 4;
+constexpr int kV2PB = 2;  // 32-point blocks per wave in every v2 launch
+
 template <int D, int NSV = 4> struct AssignV2 {
   static constexpr int KS = D / 16;
   static constexpr int NS = NSV;                         // ring depth
@@ -476,16 +417,12 @@ template <int D, int NSV = 4> struct AssignV2 {
   static constexpr int BUF = TILE_BYTES + 32 * 4;        // + -|c|²/2
   static constexpr int LDS_BYTES = NS * BUF;
   static constexpr int PIECES = 32 * (D / 8);            // 16-B pieces per tile
-  // waves per workgroup sharing one centroid stream; 8 (2 per SIMD, half the
-  // L2→LDS traffic per FLOP) measured 16–19 % slower than 4 at 100M×1024×128
-  // (profiles/kmeans_assign_tuning.md); HBMR_KMEANS_V2_WAVES picks at build time
-#ifndef HBMR_KMEANS_V2_WAVES
-#define HBMR_KMEANS_V2_WAVES 4
-#endif
-  static constexpr int WAVES = PIECES >= HBMR_KMEANS_V2_WAVES * HBMR_WAVE ? HBMR_KMEANS_V2_WAVES : 4;
+  static constexpr int WAVES = kV2Waves;
   static constexpr int THREADS = WAVES * HBMR_WAVE;
-  static constexpr int MINB = WAVES == 8 ? 1 : 2;        // → ≤ 256 VGPRs either way
+  static constexpr int MINB = 2;                         // → ≤ 256 VGPRs
   static constexpr int P = PIECES / THREADS;             // DMAs per lane per tile
+  static constexpr int PTS = WAVES * kV2PB * 32;         // points per workgroup
+  static_assert(PIECES % THREADS == 0, "a tile's pieces must tile the workgroup");
 };
 
 template <int N> __device__ __forceinline__ void vm_wait() {
@@ -562,8 +499,7 @@ inline int exact_kernel() {
   return g_exact_kernel > 0 ? g_exact_kernel : env;
 }
 
-template <int D, int PB, bool EXACT = false, bool F16 = false, bool TOP3 = false,
-          class Fin = NoFin>
+template <int D, int PB, bool EXACT = false, bool F16 = false, class Fin = NoFin>
 __device__ __forceinline__ void assign_tile_v2(const __bf16* __restrict__ X, long n,
                                                const __bf16* __restrict__ C,
                                                const float* __restrict__ chalf, int ntiles,
@@ -595,8 +531,7 @@ __device__ __forceinline__ void assign_tile_v2(const __bf16* __restrict__ X, lon
 #pragma unroll
     for (int s = 0; s < KS; ++s) bfrag[pb][s] = __builtin_bit_cast(bf16x8, row[2 * s + h]);
   }
-  typename std::conditional<EXACT, typename std::conditional<TOP3, PackedTop3, PackedTop2x8>::type,
-                            PackedArgMax>::type am[PB];
+  ArgMaxT<EXACT> am[PB];
 #pragma unroll
   for (int pb = 0; pb < PB; ++pb) am[pb].init(ntiles);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -658,8 +593,7 @@ __device__ __forceinline__ void assign_tile_v2(const __bf16* __restrict__ X, lon
   } else {
 #pragma unroll
     for (int pb = 0; pb < PB; ++pb)
-      finish_point<EXACT>(am[pb], h, p0 + pb * 32 + col, n, labels, cand, scores, margin,
-                          nullptr, cs);
+      finish_point<EXACT>(am[pb], h, p0 + pb * 32 + col, n, labels, cand, scores, margin, cs);
   }
 }
 
@@ -669,7 +603,7 @@ __global__ __launch_bounds__(kThreads, 2) void kmeans_assign_kernel(
     const float* __restrict__ chalf, int nchunks, int32_t* __restrict__ labels,
     float* __restrict__ scores) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  assign_tile<D>(X, n, C, chalf, nchunks, labels, scores, nullptr,
+  assign_tile<D>(X, n, C, chalf, nchunks, labels, scores,
                  hbmr_xcd_remap(blockIdx.x, gridDim.x), smem);
 }
 
@@ -691,44 +625,25 @@ __global__ __launch_bounds__(kThreads, 2) void kmeans_assign_top3_kernel(
     const float* __restrict__ chalf, int nchunks, int32_t* __restrict__ labels,
     int32_t* __restrict__ cand, float* __restrict__ scores, float* __restrict__ margin) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  assign_tile<D, true, F16>(X, n, C, chalf, nchunks, labels, scores, nullptr,
+  assign_tile<D, true, F16>(X, n, C, chalf, nchunks, labels, scores,
                             hbmr_xcd_remap(blockIdx.x, gridDim.x), smem, cand, margin);
 }
 
-template <int D, int PB, bool F16, bool TOP3 = false>
-__global__ __launch_bounds__(AssignV2<D>::THREADS, HBMR_EXACT_MINB) void kmeans_assign_top3_v2_kernel(
+template <int D, int PB, bool F16>
+__global__ __launch_bounds__(AssignV2<D>::THREADS, kExactMinB) void kmeans_assign_top3_v2_kernel(
     const __bf16* __restrict__ X, long n, const __bf16* __restrict__ C,
     const float* __restrict__ chalf, int ntiles, int32_t* __restrict__ labels,
     int32_t* __restrict__ cand, float* __restrict__ scores, float* __restrict__ margin) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  assign_tile_v2<D, PB, true, F16, TOP3>(X, n, C, chalf, ntiles, labels, scores,
-                                         hbmr_xcd_remap(blockIdx.x, gridDim.x), smem, cand,
-                                         margin);
+  assign_tile_v2<D, PB, true, F16>(X, n, C, chalf, ntiles, labels, scores,
+                                   hbmr_xcd_remap(blockIdx.x, gridDim.x), smem, cand, margin);
 }
 
-// 1 = the chunked kernel above, 2 = the pipelined v2 (D ≤ 128); HBMR_KMEANS_ASSIGN
-inline int assign_version(int D) {
-  static const int v = [] {
-    const char* e = getenv("HBMR_KMEANS_ASSIGN");
-    return e && e[0] == '1' ? 1 : 2;
-  }();
-  return D <= 128 ? v : 1;
-}
-
-// v2 point blocks (32 points) per wave: 2 or 3; HBMR_KMEANS_PB
-inline int v2_pb() {
-  static const int pb = [] {
-    const char* e = getenv("HBMR_KMEANS_PB");
-    return e && e[0] == '3' ? 3 : 2;
-  }();
-  return pb;
-}
-
-// points per workgroup of the assign kernel launch_*assign picks
-template <int D> int assign_pts(bool hist) {
-  if constexpr (D <= 128)
-    if (assign_version(D) == 2 && !hist) return AssignV2<D>::WAVES * v2_pb() * 32;
-  return AssignCfg<D>::PTS;
+// points per workgroup of the assign kernel launch_*assign picks: the
+// pipelined v2 for D ≤ 128, the chunked v1 for D = 256
+template <int D> constexpr int assign_pts() {
+  if constexpr (D <= 128) return AssignV2<D>::PTS;
+  else return AssignCfg<D>::PTS;
 }
 
 // ---------------------------------------------------------------------------
@@ -757,12 +672,12 @@ __device__ __forceinline__ int find_split(const SplitTable& t, long b) {
 template <int D>
 __global__ __launch_bounds__(kThreads, 2) void kmeans_assign_grouped_kernel(
     const SplitTable tbl, const __bf16* __restrict__ C, const float* __restrict__ chalf,
-    int nchunks, int32_t* __restrict__ labels, uint32_t* __restrict__ hist) {
+    int nchunks, int32_t* __restrict__ labels) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const long b = hbmr_xcd_remap(blockIdx.x, gridDim.x);
   const int s = __builtin_amdgcn_readfirstlane(find_split(tbl, b));
   assign_tile<D>(tbl.X[s], tbl.n[s], C, chalf, nchunks, labels + tbl.off[s], nullptr,
-                 hist + (size_t)s * tbl.k, b - tbl.blk[s], smem);
+                 b - tbl.blk[s], smem);
 }
 
 template <int D, int PB>
@@ -780,8 +695,8 @@ __global__ __launch_bounds__(AssignV2<D>::THREADS, AssignV2<D>::MINB) void kmean
 // top-3 assign ran at 57 % MFMA busy against 67 % for a long dispatch): the
 // batch's labels / scores and the two-row cand / margin arrays are indexed by
 // the batch position (split offset + row), second rows at stride tbl.off[nsplit]
-template <int D, int PB, bool F16, bool TOP3>
-__global__ __launch_bounds__(AssignV2<D>::THREADS, HBMR_EXACT_MINB) void
+template <int D, int PB, bool F16>
+__global__ __launch_bounds__(AssignV2<D>::THREADS, kExactMinB) void
 kmeans_assign_top3_grouped_v2_kernel(const SplitTable tbl, const __bf16* __restrict__ C,
                                      const float* __restrict__ chalf, int ntiles,
                                      int32_t* __restrict__ labels, int32_t* __restrict__ cand,
@@ -791,9 +706,8 @@ kmeans_assign_top3_grouped_v2_kernel(const SplitTable tbl, const __bf16* __restr
   const long b = hbmr_xcd_remap(blockIdx.x, gridDim.x);
   const int s = __builtin_amdgcn_readfirstlane(find_split(tbl, b));
   const long o = tbl.off[s];
-  assign_tile_v2<D, PB, true, F16, TOP3>(tbl.X[s], tbl.n[s], C, chalf, ntiles, labels + o,
-                                         scores + o, b - tbl.blk[s], smem, cand + o, margin + o,
-                                         total);
+  assign_tile_v2<D, PB, true, F16>(tbl.X[s], tbl.n[s], C, chalf, ntiles, labels + o, scores + o,
+                                   b - tbl.blk[s], smem, cand + o, margin + o, total);
 }
 
 // ---------------------------------------------------------------------------
@@ -1192,7 +1106,7 @@ __global__ __launch_bounds__(256) void kmeans_segsum_kernel(
 }
 
 // ---- grouped sorted combiner ------------------------------------------------------
-// hist[s][k] comes fused from the grouped assign.  Every scatter workgroup
+// hist[s][k] comes from kmeans_hist_grouped_kernel.  Every scatter workgroup
 // rebuilds the exclusive scan of its split's histogram in LDS (k ≤ 8192: a few
 // µs) so no separate scan launch or grid-wide sync is needed; the workgroup
 // with local index 0 of each split also publishes offsets[s] (for the segsum
@@ -1226,8 +1140,7 @@ __device__ void block_exclusive_scan(const uint32_t* __restrict__ in, int k, uin
   __syncthreads();
 }
 
-// Per-split label histogram from the labels array (alternative to the fused
-// histogram atomics in the assign epilogue): LDS bins, one flush per block.
+// Per-split label histogram from the labels array: LDS bins, one flush per block.
 constexpr long kHistPts = 16384;
 __global__ __launch_bounds__(256) void kmeans_hist_grouped_kernel(const SplitTable tbl,
                                                                   const int32_t* __restrict__ labels,
@@ -1600,40 +1513,34 @@ int launch_assign(const void* X, long n, const void* C, const float* chalf, int 
   using Cfg = AssignCfg<D>;
   if (n <= 0) return 0;
   if (k_pad % kCK) return (int)hipErrorInvalidValue;
-  const int pts = assign_pts<D>(false);
+  constexpr int pts = assign_pts<D>();
   const long nblk = (n + pts - 1) / pts;
   if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
   if constexpr (D <= 128) {
-    if (assign_version(D) == 2) {
-      auto kern = v2_pb() == 3 ? kmeans_assign_v2_kernel<D, 3> : kmeans_assign_v2_kernel<D, 2>;
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(AssignV2<D>::THREADS),
-                         AssignV2<D>::LDS_BYTES, st, reinterpret_cast<const __bf16*>(X), n,
-                         reinterpret_cast<const __bf16*>(C), chalf, k_pad / 32, labels, scores);
-      return (int)hipGetLastError();
-    }
+    hipLaunchKernelGGL((kmeans_assign_v2_kernel<D, kV2PB>), dim3((unsigned)nblk),
+                       dim3(AssignV2<D>::THREADS), AssignV2<D>::LDS_BYTES, st,
+                       reinterpret_cast<const __bf16*>(X), n, reinterpret_cast<const __bf16*>(C),
+                       chalf, k_pad / 32, labels, scores);
+  } else {
+    hipLaunchKernelGGL(kmeans_assign_kernel<D>, dim3((unsigned)nblk), dim3(kThreads),
+                       Cfg::LDS_BYTES, st, reinterpret_cast<const __bf16*>(X), n,
+                       reinterpret_cast<const __bf16*>(C), chalf, k_pad / kCK, labels, scores);
   }
-  hipLaunchKernelGGL(kmeans_assign_kernel<D>, dim3((unsigned)nblk), dim3(kThreads),
-                     Cfg::LDS_BYTES, st, reinterpret_cast<const __bf16*>(X), n,
-                     reinterpret_cast<const __bf16*>(C), chalf, k_pad / kCK, labels, scores);
   return (int)hipGetLastError();
 }
 
 template <int D>
 void launch_grouped_assign(long nb, const SplitTable& t, const void* C, const float* chalf,
-                           int k_pad, int32_t* labels, uint32_t* hist, hipStream_t st) {
+                           int k_pad, int32_t* labels, hipStream_t st) {
   if constexpr (D <= 128) {
-    if (assign_version(D) == 2 && hist == nullptr) {
-      auto kern = v2_pb() == 3 ? kmeans_assign_grouped_v2_kernel<D, 3>
-                               : kmeans_assign_grouped_v2_kernel<D, 2>;
-      hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(AssignV2<D>::THREADS),
-                         AssignV2<D>::LDS_BYTES, st, t, reinterpret_cast<const __bf16*>(C),
-                         chalf, k_pad / 32, labels);
-      return;
-    }
+    hipLaunchKernelGGL((kmeans_assign_grouped_v2_kernel<D, kV2PB>), dim3((unsigned)nb),
+                       dim3(AssignV2<D>::THREADS), AssignV2<D>::LDS_BYTES, st, t,
+                       reinterpret_cast<const __bf16*>(C), chalf, k_pad / 32, labels);
+  } else {
+    hipLaunchKernelGGL(kmeans_assign_grouped_kernel<D>, dim3((unsigned)nb), dim3(kThreads),
+                       AssignCfg<D>::LDS_BYTES, st, t, reinterpret_cast<const __bf16*>(C), chalf,
+                       k_pad / kCK, labels);
   }
-  hipLaunchKernelGGL(kmeans_assign_grouped_kernel<D>, dim3((unsigned)nb), dim3(kThreads),
-                     AssignCfg<D>::LDS_BYTES, st, t, reinterpret_cast<const __bf16*>(C), chalf,
-                     k_pad / kCK, labels, hist);
 }
 
 template <typename T, int D>
@@ -2076,10 +1983,7 @@ __device__ __forceinline__ void rows_dist2(const double (&xv)[8 * NM],
 // neighbours per Elkan step: 2 keeps v2 at 128 VGPRs (4 waves per SIMD; 4 rows
 // in flight take 134, 3 waves).  The exit bound refreshes every step, and the
 // minimum over any superset of the one-at-a-time walk is the same winner.
-#ifndef HBMR_ELKAN_STEP
-#define HBMR_ELKAN_STEP 2
-#endif
-constexpr int kElkanStep = HBMR_ELKAN_STEP;
+constexpr int kElkanStep = 2;
 
 template <int NM>
 __global__ __launch_bounds__(256) void kmeans_refine_v2_kernel(
@@ -2376,15 +2280,6 @@ constexpr int kQ1Per = 4;            // points per thread in the step-1 scan
 constexpr int kQ2Lanes = 8;          // lanes per Q1 entry in step 2
 constexpr int kQ2Per = HBMR_WAVE / kQ2Lanes;
 constexpr int kRefineGrid = 2048;    // persistent grid of q2 and q3
-// HBMR_REFINE_GRID (read once) overrides it, for tuning runs
-inline long refine_grid() {
-  static const long g = [] {
-    const char* e = getenv("HBMR_REFINE_GRID");
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? v : (long)kRefineGrid;
-  }();
-  return g;
-}
 // workspace header: Q1 / Q2 shard counts (8 + 8 u32) and the sharded stats
 // (8 shards x 4 u64 at kStatsOff): one word per stat took every block's
 // atomic at the kernels' tails; kmeans_refine_stats_kernel folds them
@@ -2416,7 +2311,7 @@ inline RefineLayout refine_layout(int nsplit, const long* ns) {
   // the fused top-3 epilogue appends from 256-point workgroups, shard =
   // blockIdx % kQShards: at most ceil(nb / kQShards) workgroups per shard
   L.cap1 = std::max<long>(cap1, ceil_div(nb_fused, kQShards) * 256);
-  L.g2 = (unsigned)std::max<long>(1, std::min<long>(refine_grid(), ceil_div(total, 4 * kQ2Per)));
+  L.g2 = (unsigned)std::max<long>(1, std::min<long>(kRefineGrid, ceil_div(total, 4 * kQ2Per)));
   const long per_iter = (long)L.g2 * 4 * kQ2Per;           // Q1 entries per grid iteration
   L.cap2 = ceil_div(L.g2, kQShards) * 4 * kQ2Per * std::max<long>(1, ceil_div(total, per_iter));
   L.off1 = kRefineHdr;
@@ -2709,11 +2604,9 @@ struct FusedQ1Fin {
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i) insert3(v, c, ov[i], oc[i]);
-      if constexpr (HasTracks<AM>::value) {
-        if (((c[0] ^ c[1]) & AM::TMASK) == 0) {
-          v[2] = v[0];
-          c[2] = c[0];
-        }
+      if (((c[0] ^ c[1]) & AM::TMASK) == 0) {
+        v[2] = v[0];
+        c[2] = c[0];
       }
       const long p = p0 + pb * 32 + col;
       flag[pb] = false;
@@ -2952,7 +2845,7 @@ struct TopQ1Table {       // the batch's splits, by value (X, per-point norms)
 };
 
 template <int D, bool F16>
-__global__ __launch_bounds__(AssignV2<D>::THREADS, HBMR_EXACT_MINB) void
+__global__ __launch_bounds__(AssignV2<D>::THREADS, kExactMinB) void
 kmeans_assign_top3_q1_grouped_kernel(const TopQ1Table tbl, const __bf16* __restrict__ C,
                                      const float* __restrict__ chalf, int ntiles,
                                      int32_t* __restrict__ labels, FusedQ1Fin fin) {
@@ -2969,15 +2862,14 @@ kmeans_assign_top3_q1_grouped_kernel(const TopQ1Table tbl, const __bf16* __restr
   fin.xbn2 = tbl.xbn2[s];
   fin.xerr = tbl.xerr[s];
   fin.sidx = s;
-  assign_tile_v2<D, 2, true, F16, false, FusedQ1Fin>(
-      tbl.X[s], tbl.off[s + 1] - o, C, chalf,
-                                                     ntiles, labels + o, nullptr, b - tbl.blk[s],
-                                                     smem, nullptr, nullptr, -1, &fin);
+  assign_tile_v2<D, 2, true, F16, FusedQ1Fin>(tbl.X[s], tbl.off[s + 1] - o, C, chalf, ntiles,
+                                              labels + o, nullptr, b - tbl.blk[s], smem, nullptr,
+                                              nullptr, -1, &fin);
 }
 
-// v3 (see assign_tile_v3): HBMR_EXACT_MINB workgroups of 4 waves per CU
+// v3 (see assign_tile_v3): kExactMinB workgroups of 4 waves per CU
 template <int D, bool F16>
-__global__ __launch_bounds__(256, HBMR_EXACT_MINB) void kmeans_assign_top3_q1_v3_kernel(
+__global__ __launch_bounds__(256, kExactMinB) void kmeans_assign_top3_q1_v3_kernel(
     const TopQ1Table tbl, const __bf16* __restrict__ Ct, const float* __restrict__ chalf,
     int ntiles, int32_t* __restrict__ labels, FusedQ1Fin fin) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -3132,7 +3024,7 @@ struct GapTable {
 // (the list lengths live on the device); a workgroup past its split's list
 // leaves before it stages anything.
 template <int D, bool F16>
-__global__ __launch_bounds__(256, HBMR_EXACT_MINB) void kmeans_assign_top3_q1_bounded_kernel(
+__global__ __launch_bounds__(256, kExactMinB) void kmeans_assign_top3_q1_bounded_kernel(
     const TopQ1Table tbl, const GapTable gt, const __bf16* __restrict__ Ct,
     const float* __restrict__ chalf, int ntiles, int32_t* __restrict__ labels, FusedQ1Fin fin,
     const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ idx,
@@ -3444,15 +3336,6 @@ __global__ void kmeans_refine_stats_kernel(const unsigned long long* __restrict_
   if (v) stats[t] += v;
 }
 
-int refine_version() {
-  static int v = 0;
-  if (!v) {
-    const char* e = getenv("HBMR_REFINE");
-    v = (e && atoi(e) == 1) ? 1 : 2;
-  }
-  return v;
-}
-
 template <int D, bool F16>
 int launch_assign_top3_grouped(int nsplit, const void* const* X, const long* n, const void* C,
                                const float* chalf, int k_pad, int32_t* labels, int32_t* cand,
@@ -3464,7 +3347,7 @@ int launch_assign_top3_grouped(int nsplit, const void* const* X, const long* n, 
     SplitTable t;
     memset(&t, 0, sizeof(t));
     t.nsplit = nsplit;
-    constexpr int pts = AssignV2<D>::WAVES * 2 * 32;
+    constexpr int pts = AssignV2<D>::PTS;
     long total = 0, nb = 0;
     for (int i = 0; i < nsplit; ++i) {
       if (n[i] < 0) return (int)hipErrorInvalidValue;
@@ -3478,15 +3361,10 @@ int launch_assign_top3_grouped(int nsplit, const void* const* X, const long* n, 
     t.blk[nsplit] = nb;
     if (nb == 0) return 0;
     if (nb > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    static const bool top3 = [] {
-      const char* e = getenv("HBMR_EXACT_EPI");
-      return e && strcmp(e, "top3") == 0;
-    }();
-    auto kern = top3 ? kmeans_assign_top3_grouped_v2_kernel<D, 2, F16, true>
-                     : kmeans_assign_top3_grouped_v2_kernel<D, 2, F16, false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(AssignV2<D>::THREADS),
-                       AssignV2<D>::LDS_BYTES, st, t, reinterpret_cast<const __bf16*>(C), chalf,
-                       k_pad / 32, labels, cand, scores, margin, total);
+    hipLaunchKernelGGL((kmeans_assign_top3_grouped_v2_kernel<D, kV2PB, F16>), dim3((unsigned)nb),
+                       dim3(AssignV2<D>::THREADS), AssignV2<D>::LDS_BYTES, st, t,
+                       reinterpret_cast<const __bf16*>(C), chalf, k_pad / 32, labels, cand, scores,
+                       margin, total);
     return (int)hipGetLastError();
   }
 }
@@ -3497,31 +3375,20 @@ int launch_assign_top3(const void* X, long n, const void* C, const float* chalf,
                        hipStream_t st) {
   if (n <= 0) return 0;
   if (k_pad % kCK) return (int)hipErrorInvalidValue;
-  if constexpr (D <= 128) {
-    if (assign_version(D) == 2) {
-      const int pts = AssignV2<D>::WAVES * 2 * 32;
-      const long nblk = (n + pts - 1) / pts;
-      if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
-      // HBMR_EXACT_EPI=top3: the full running top-3 epilogue (PackedTop3)
-      static const bool top3 = [] {
-        const char* e = getenv("HBMR_EXACT_EPI");
-        return e && strcmp(e, "top3") == 0;
-      }();
-      auto kern = top3 ? kmeans_assign_top3_v2_kernel<D, 2, F16, true>
-                       : kmeans_assign_top3_v2_kernel<D, 2, F16, false>;
-      hipLaunchKernelGGL(kern, dim3((unsigned)nblk),
-                         dim3(AssignV2<D>::THREADS), AssignV2<D>::LDS_BYTES, st,
-                         reinterpret_cast<const __bf16*>(X), n, reinterpret_cast<const __bf16*>(C),
-                         chalf, k_pad / 32, labels, cand, scores, margin);
-      return (int)hipGetLastError();
-    }
-  }
-  const long nblk = (n + AssignCfg<D>::PTS - 1) / AssignCfg<D>::PTS;
+  constexpr int pts = assign_pts<D>();
+  const long nblk = (n + pts - 1) / pts;
   if (nblk > 0x7fffffffL) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL((kmeans_assign_top3_kernel<D, F16>), dim3((unsigned)nblk), dim3(kThreads),
-                     AssignCfg<D>::LDS_BYTES, st, reinterpret_cast<const __bf16*>(X), n,
-                     reinterpret_cast<const __bf16*>(C), chalf, k_pad / kCK, labels, cand, scores,
-                     margin);
+  if constexpr (D <= 128) {
+    hipLaunchKernelGGL((kmeans_assign_top3_v2_kernel<D, kV2PB, F16>), dim3((unsigned)nblk),
+                       dim3(AssignV2<D>::THREADS), AssignV2<D>::LDS_BYTES, st,
+                       reinterpret_cast<const __bf16*>(X), n, reinterpret_cast<const __bf16*>(C),
+                       chalf, k_pad / 32, labels, cand, scores, margin);
+  } else {
+    hipLaunchKernelGGL((kmeans_assign_top3_kernel<D, F16>), dim3((unsigned)nblk), dim3(kThreads),
+                       AssignCfg<D>::LDS_BYTES, st, reinterpret_cast<const __bf16*>(X), n,
+                       reinterpret_cast<const __bf16*>(C), chalf, k_pad / kCK, labels, cand,
+                       scores, margin);
+  }
   return (int)hipGetLastError();
 }
 
@@ -3665,7 +3532,7 @@ long hbmr_kmeans_batch_workspace_bytes(long total_n, int ntasks, int k) {
                 ws_align((size_t)total_n * 4));
 }
 
-// Grouped path: 1 memset + 3 launches for the whole batch (assign+hist,
+// Grouped path: 1 memset + 4 launches for the whole batch (assign, histogram,
 // scan+scatter, segmented sum).  labels must hold Σ n[t] entries.
 static int map_batch_grouped(int ntasks, const void* const* X, const long* n, int dp,
                              const void* C, const float* chalf, int k_pad, int k,
@@ -3689,18 +3556,13 @@ static int map_batch_grouped(int ntasks, const void* const* X, const long* n, in
   uint32_t* offsets = reinterpret_cast<uint32_t*>(w + 2 * hb);
   uint32_t* perm = reinterpret_cast<uint32_t*>(w + 2 * hb + ws_align((size_t)ntasks * (k + 1) * 4));
   HBMR_RETURN_IF_ERROR(hipMemsetAsync(hist, 0, 2 * hb, st));  // hist + cursor
-  // 1. assign (+ histogram: fused atomics in the assign epilogue, or a separate
-  //    LDS-binned pass over the labels; HBMR_KMEANS_FUSED_HIST=1 selects fused)
-  static const bool fused = [] {
-    const char* e = getenv("HBMR_KMEANS_FUSED_HIST");
-    return e != nullptr && e[0] == '1';
-  }();
+  // 1. assign, then the histogram as an LDS-binned pass over the labels
   long nb = 0;
   int pts = 0;
   switch (dp) {
-    case 64: pts = assign_pts<64>(fused); break;
-    case 128: pts = assign_pts<128>(fused); break;
-    case 256: pts = assign_pts<256>(fused); break;
+    case 64: pts = assign_pts<64>(); break;
+    case 128: pts = assign_pts<128>(); break;
+    case 256: pts = assign_pts<256>(); break;
     default: return (int)hipErrorInvalidValue;
   }
   for (int i = 0; i < ntasks; ++i) {
@@ -3710,29 +3572,22 @@ static int map_batch_grouped(int ntasks, const void* const* X, const long* n, in
   t.blk[ntasks] = nb;
   if (nb > 0) {
     switch (dp) {
-#define HBMR_GA(DD)                                                                          \
-  case DD:                                                                                   \
-    launch_grouped_assign<DD>(nb, t, C, chalf, k_pad, labels, fused ? hist : nullptr, st);   \
-    break;
-      HBMR_GA(64)
-      HBMR_GA(128)
-      HBMR_GA(256)
-#undef HBMR_GA
+      case 64: launch_grouped_assign<64>(nb, t, C, chalf, k_pad, labels, st); break;
+      case 128: launch_grouped_assign<128>(nb, t, C, chalf, k_pad, labels, st); break;
+      case 256: launch_grouped_assign<256>(nb, t, C, chalf, k_pad, labels, st); break;
     }
     HBMR_RETURN_IF_ERROR(hipGetLastError());
   }
-  if (!fused) {
-    long hb_blocks = 0;
-    for (int i = 0; i < ntasks; ++i) {
-      t.blk[i] = hb_blocks;
-      hb_blocks += (n[i] + kHistPts - 1) / kHistPts;
-    }
-    t.blk[ntasks] = hb_blocks;
-    if (hb_blocks > 0) {
-      hipLaunchKernelGGL(kmeans_hist_grouped_kernel, dim3((unsigned)hb_blocks), dim3(256),
-                         (size_t)k * 4, st, t, labels, hist);
-      HBMR_RETURN_IF_ERROR(hipGetLastError());
-    }
+  long hb_blocks = 0;
+  for (int i = 0; i < ntasks; ++i) {
+    t.blk[i] = hb_blocks;
+    hb_blocks += (n[i] + kHistPts - 1) / kHistPts;
+  }
+  t.blk[ntasks] = hb_blocks;
+  if (hb_blocks > 0) {
+    hipLaunchKernelGGL(kmeans_hist_grouped_kernel, dim3((unsigned)hb_blocks), dim3(256),
+                       (size_t)k * 4, st, t, labels, hist);
+    HBMR_RETURN_IF_ERROR(hipGetLastError());
   }
   // 2. scan + scatter (+ counts, offsets)
   nb = 0;
@@ -3937,9 +3792,9 @@ int hbmr_kmeans_map_batch_delta(int ntasks, const void* const* X, const long* n,
   t.k = k;
   int pts = 0;
   switch (dp) {
-    case 64: pts = assign_pts<64>(false); break;
-    case 128: pts = assign_pts<128>(false); break;
-    case 256: pts = assign_pts<256>(false); break;
+    case 64: pts = assign_pts<64>(); break;
+    case 128: pts = assign_pts<128>(); break;
+    case 256: pts = assign_pts<256>(); break;
     default: return (int)hipErrorInvalidValue;
   }
   long total = 0, nb = 0;
@@ -3955,9 +3810,9 @@ int hbmr_kmeans_map_batch_delta(int ntasks, const void* const* X, const long* n,
   if (nb > 0x7fffffffL) return (int)hipErrorInvalidValue;
   if (nb > 0) {
     switch (dp) {
-      case 64: launch_grouped_assign<64>(nb, t, C, chalf, k_pad, labels, nullptr, st); break;
-      case 128: launch_grouped_assign<128>(nb, t, C, chalf, k_pad, labels, nullptr, st); break;
-      case 256: launch_grouped_assign<256>(nb, t, C, chalf, k_pad, labels, nullptr, st); break;
+      case 64: launch_grouped_assign<64>(nb, t, C, chalf, k_pad, labels, st); break;
+      case 128: launch_grouped_assign<128>(nb, t, C, chalf, k_pad, labels, st); break;
+      case 256: launch_grouped_assign<256>(nb, t, C, chalf, k_pad, labels, st); break;
     }
     HBMR_RETURN_IF_ERROR(hipGetLastError());
   }
@@ -4236,7 +4091,7 @@ int hbmr_kmeans_refine_f32(const float* X32, long n, int d, int ldx, const float
   // v2 wants whole 8-feature lane slices and 16-byte aligned rows
   const bool v2_ok = d % 8 == 0 && ldx % 4 == 0 && ((uintptr_t)X32 & 15) == 0 &&
                      ((uintptr_t)C32 & 15) == 0;
-  if (v2_ok && refine_version() == 2) {
+  if (v2_ok) {
     auto kern = d <= 128 ? kmeans_refine_v2_kernel<1> : kmeans_refine_v2_kernel<2>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, st, X32, n, d, ldx, xnorm,
                        xbn2, xerr, C32, k, cnorm, cmax, cerr, cerrmax, pack_rel, nbr_idx,
@@ -4538,4 +4393,3 @@ int hbmr_kmeans_refine_batch_finish(int nsplit, const long* ns, const float* con
 }
 
 }  // extern "C"
-

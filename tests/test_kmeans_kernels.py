@@ -116,7 +116,10 @@ def test_cpu_map_matches_reference():
 @pytest.mark.gpu
 @pytest.mark.parametrize("k,dp,sizes", [(1024, 128, [5000, 1, 70000, 4096, 12345]),
                                         (64, 128, [3000, 9000]),
-                                        (300, 64, [777, 20000, 5])])
+                                        (300, 64, [777, 20000, 5]),
+                                        # dp = 256: the chunked v1 grouped assign,
+                                        # 128 points per workgroup
+                                        (40, 256, [129, 1, 128, 300])])
 def test_map_batch_matches_per_split(k, dp, sizes):
     dev = torch.device("cuda")
     g = torch.Generator(device="cpu").manual_seed(3)
