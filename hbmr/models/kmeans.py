@@ -7,7 +7,8 @@ DistributedCache):
 * map (per split)      : assign every point to its nearest centroid and
                          combine in-task to per-cluster (sum, count) partials.
                          GPU slots run the MFMA kernels of
-                         native/kernels/kmeans.hip on the HBM-resident split;
+                         native/kernels/kmeans.hip (sections under
+                         native/kernels/kmeans/) on the HBM-resident split;
                          CPU slots run the native C++ map (native/cpu).
                          Partials are int64 fixed point → exact and
                          placement-independent.

@@ -1,4 +1,5 @@
-"""K-Means map/combine/reduce ops on MI355X (HIP kernels in native/kernels/kmeans.hip).
+"""K-Means map/combine/reduce ops on MI355X (entry points in native/kernels/kmeans.hip,
+HIP kernels in its sections native/kernels/kmeans/*.h).
 
 Data layout contract (built by :class:`hbmr.gpu.split_cache.SplitCache`):
 

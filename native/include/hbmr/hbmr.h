@@ -14,7 +14,7 @@ extern "C" {
 
 typedef struct ihipStream_t* hbmr_stream_t;
 
-// ---- K-Means (native/kernels/kmeans.hip) -----------------------------------
+// ---- K-Means (native/kernels/kmeans.hip; kernels in native/kernels/kmeans/*.h) ----
 #ifndef HBMR_NO_HIP_DECLS
 #include <hip/hip_runtime_api.h>
 int hbmr_kmeans_assign_bf16(const void* X, long n, int dp, const void* C, const float* chalf,

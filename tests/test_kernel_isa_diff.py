@@ -27,6 +27,8 @@ Disassembly of section .text:
 
 0000000000001a00 <void (anonymous namespace)::k_gone<3>(int*)>:
 \ts_endpgm                                                   // 000000001A00: BF810000
+\ts_nop 0                                                    // 000000001A04: BF800000
+\ts_nop 0                                                    // 000000001A08: BF800000
 """
 
 # k_assign moved and lost a template argument, same instructions; k_plain lost
@@ -55,6 +57,8 @@ def test_normalise_strips_addresses_targets_and_padding():
         "s_load_dwordx2 s[4:5], s[0:1], 0x0", "v_cmp_gt_i32_e32 vcc, s13, v0",
         "s_cbranch_execz 33", "s_endpgm"]
     assert old["k_plain"] == ["v_mov_b32_e32 v1, 0", "s_endpgm"]
+    # the s_nop run that closes .text is padding of whichever kernel is last
+    assert old["k_gone<3>"] == ["s_endpgm"]
 
 
 def test_compare_pairs_renamed_kernels_and_honours_allow():

@@ -14,8 +14,9 @@ which writes kmeans-hip-amdgcn-amd-amdhsa-gfx950.out, then
 
 Each object is disassembled with ROCm's llvm-objdump and split per symbol;
 addresses, the address/encoding comments, <sym+0x...> branch targets and the
-alignment padding after a kernel ("...") are stripped, so a kernel that merely
-moved compares equal.  Names are demangled,
+alignment padding after a kernel ("...", and the s_nop run after the last
+kernel of .text) are stripped, so a kernel that merely moved compares equal.
+Names are demangled,
 without "(anonymous namespace)::" and the parameter list, e.g.
 "kmeans_assign_v2_kernel<64, 2>".  --rename pairs a kernel of the first object
 whose template list shrank with its new name.  Prints REMOVED / ADDED / DIFF
@@ -48,6 +49,9 @@ def normalise(disasm: str) -> dict:
             text = " ".join(line.split("//", 1)[0].split())
             if text and text != "...":      # "...": elided zero padding up to the next symbol
                 cur.append(text)
+    for ins in out.values():        # the s_nop run that closes .text lands in whichever kernel
+        while ins and ins[-1] == "s_nop 0":     # is last; it follows s_endpgm and never runs
+            ins.pop()
     return out
 
 
