@@ -19,12 +19,18 @@ MI355X design:
 * shuffle: one all-to-all-v per tracker over RCCL/xGMI (each GPU owns a
   contiguous range of partitions) — the HTTP shuffle + merge of the
   reference (ReduceTask.java:1231-2514) disappears;
-* reduce (collective, one per tracker): per group of consecutive partitions,
-  collect the pieces every map produced, radix-sort the keys (8 passes over
-  the high 8 key bytes, runs of equal high words ordered by the last 2 bytes),
-  gather the 100-byte records once (4 records in flight per lane), verify
-  order locally and against the neighbouring ranks' boundary keys
-  (TeraValidate), and write ``part-NNNNN`` files if an output directory is set.
+* reduce (collective, one per tracker).  One rank: per group of consecutive
+  partitions, collect from every map one word per record — a dense 32-bit
+  window of the key above the packed record id (split << 24 | row) — sort it
+  keys-only (onesweep, 4 passes), gather the 100-byte records once in 16-byte
+  pieces (the gather also writes the sorted key words), and order the runs
+  the window left tied by the full key in place.  A group too large to pack
+  sorts (key, id) pairs over 40 bits; a run too long for the tie fix sends the
+  group through the full 80-bit key sort and a permutation (v3).  Several
+  ranks: each sorts what the shuffle brought it, or merges sorted runs.  Every
+  path verifies order locally and against the neighbouring ranks' boundary
+  keys (TeraValidate) and writes ``part-NNNNN`` files if an output directory
+  is set.  Spill mode merges host-resident sorted runs group by group.
 
 CPU slots run the same steps with numpy (hbmr.ops.sort CPU twins).
 """
@@ -83,9 +89,21 @@ def _s64(x: int) -> int:
     return ((x + (1 << 63)) % (1 << 64)) - (1 << 63)
 
 
-def _file_records(path):
-    n = os.path.getsize(path) // S.RECORD
-    return n
+class _KeyEnds:
+    """The first key of the first group and the last key of the latest one
+    (``(hi, lo)`` 1-element slices, no host read): a reduce's boundary keys;
+    ``last`` is also what the next group's first key is checked against."""
+
+    first = last = None
+
+    def add(self, hs, ls):
+        if self.first is None:
+            self.first = (hs[:1], ls[:1])
+        self.last = (hs[-1:], ls[-1:])
+
+    def stats(self, bad, csum):
+        """The reduce's statistics row: [out of order, checksum, first, last]."""
+        return torch.cat([bad.reshape(1), csum.reshape(1), *self.first, *self.last])
 
 
 _SPLITTER_MEMO: dict = {}
@@ -168,7 +186,7 @@ class TeraSortSplitJob(SplitJob):
                        if not f.startswith(("_", ".")))
         out = []
         for f in files:
-            n = _file_records(f)
+            n = os.path.getsize(f) // S.RECORD
             for a in range(0, n, self.split_rows):
                 m = min(self.split_rows, n - a)
                 out.append(("file", {"path": f, "first": a, "rows": m}, m))
@@ -295,8 +313,7 @@ class TeraSortSplitJob(SplitJob):
     def map_gpu(self, ctx, data):
         return self._map_spill(ctx, data) if self.spill else self._map(ctx, data)
 
-    def map_cpu(self, ctx, data):
-        return self._map_spill(ctx, data) if self.spill else self._map(ctx, data)
+    map_cpu = map_gpu       # the same steps; the ops choose by the records' device
 
     def map_gpu_batch(self, ctxs, datas):
         return [self.map_gpu(c, d) for c, d in zip(ctxs, datas)]
@@ -439,22 +456,13 @@ class TeraSortSplitJob(SplitJob):
         bases = [o["records"] for o in outs]
         # (out of order, checksum) and the stats kernel's scratch
         gstats = torch.zeros(S.GROUP_STATS_LEN, dtype=torch.int64, device=dev)
-        prev_last = None
-        first = last = None
+        ends = _KeyEnds()
         n = 0
         sizes = (offs[:, 1:] - offs[:, :-1]).sum(axis=0)     # records per partition
-        groups, pa = [], 0
         # a group stays below the packed-key sort's record limit when its
         # partitions allow (one larger partition sorts as pairs)
         lim = min(self.group_bytes // S.RECORD, S.PACK_GROUP_MAX - 1) if self.gid else \
             self.group_bytes // S.RECORD
-        while pa < nparts:
-            pb, acc = pa, 0
-            while pb < nparts and (pb == pa or acc + int(sizes[pb]) <= lim):
-                acc += int(sizes[pb])
-                pb += 1
-            groups.append((pa, pb))
-            pa = pb
         spl_hi = [int(h[:16], 16) for h in outs[0].get("splitters") or []] if nparts > 1 else []
         # the key alphabet [0, 2^bits) holding every key byte of the high
         # words (the maps' OR of them): the packed sort's dense window needs
@@ -465,7 +473,7 @@ class TeraSortSplitJob(SplitJob):
             for x in torch.stack([o["kbytes"][0].to(dev) for o in outs]).tolist():
                 orb |= int(x)
             alphabet = (0, 1 << max(1, orb.bit_length()))
-        for pa, pb in groups:
+        for pa, pb in self._groups(sizes, nparts, lim):
             starts = offs[:, pa]
             lens = offs[:, pb] - offs[:, pa]
             m = int(lens.sum())
@@ -496,35 +504,38 @@ class TeraSortSplitJob(SplitJob):
                     flags = flag if flags is None else flags + flag
             # order within the group and across the seam to the previous one,
             # and the key checksum, in one pass into gstats (no host read)
-            S.tera_group_stats(hs, ls, prev_last, gstats)
-            prev_last = (hs[-1:], ls[-1:])
-            if first is None:
-                first = (hs[:1], ls[:1])
-            last = (hs[-1:], ls[-1:])
+            S.tera_group_stats(hs, ls, ends.last, gstats)
+            ends.add(hs, ls)
             n += m
             if self.out:
-                at, items = 0, []
-                for p in range(pa, pb):
-                    items.append((p, recs[at:at + int(sizes[p])]))
-                    at += int(sizes[p])
-                self._write_parts(ctx, items)
+                self._write_group(ctx, recs, sizes, pa, pb)
             del recs
-        if first is None:
+        if ends.first is None:
             return 0, None, flags
-        return n, torch.cat([gstats[:2], first[0], first[1], last[0], last[1]]), flags
+        return n, ends.stats(gstats[0], gstats[1]), flags
 
-    def _groups(self, sizes, nparts, limit):
-        """Consecutive partitions in groups of at most ``limit`` record bytes
-        (a single larger partition forms its own group)."""
+    @staticmethod
+    def _groups(sizes, nparts, limit):
+        """Consecutive partitions [pa, pb) in groups of at most ``limit``
+        records (a single larger partition forms its own group)."""
         groups, pa = [], 0
         while pa < nparts:
             pb, acc = pa, 0
-            while pb < nparts and (pb == pa or (acc + int(sizes[pb])) * S.RECORD <= limit):
+            while pb < nparts and (pb == pa or acc + int(sizes[pb]) <= limit):
                 acc += int(sizes[pb])
                 pb += 1
             groups.append((pa, pb))
             pa = pb
         return groups
+
+    def _write_group(self, ctx, recs, sizes, pa, pb):
+        """Cut a sorted group of the partitions [pa, pb) at their sizes and
+        write the part files together."""
+        at, items = 0, []
+        for p in range(pa, pb):
+            items.append((p, recs[at:at + int(sizes[p])]))
+            at += int(sizes[p])
+        self._write_parts(ctx, items)
 
     def _reduce_spill(self, ctx, outs, offs, nparts, dev):
         """Out-of-core reduce (ReduceTask's merge of spilled map outputs,
@@ -534,11 +545,11 @@ class TeraSortSplitJob(SplitJob):
         keys (merge path, log2 #runs passes) and the records gathered in
         merged order; peak HBM is about 2.3x the group."""
         sizes = (offs[:, 1:] - offs[:, :-1]).sum(axis=0)
-        limit = self.budget // 3 if self.budget > 0 else self.group_bytes
+        limit = (self.budget // 3 if self.budget > 0 else self.group_bytes) // S.RECORD
         cuda = dev is not None and getattr(dev, "type", "") == "cuda"
         zero = torch.zeros((), dtype=torch.int64, device=dev)
         bad, csum = zero.clone(), zero.clone()
-        prev_last = first = last = None
+        ends = _KeyEnds()
         n = 0
         for pa, pb in self._groups(sizes, nparts, limit):
             lens = offs[:, pb] - offs[:, pa]
@@ -561,25 +572,17 @@ class TeraSortSplitJob(SplitJob):
             recs = S.gather_records(buf, idx)
             del buf, idx
             bad = bad + S.count_unsorted_dev(hs, ls)
-            if prev_last is not None:
-                bad = bad + S.pair_greater(prev_last, (hs[:1], ls[:1]))
-            prev_last = (hs[-1:], ls[-1:])
-            if first is None:
-                first = (hs[:1], ls[:1])
-            last = (hs[-1:], ls[-1:])
+            if ends.last is not None:
+                bad = bad + S.pair_greater(ends.last, (hs[:1], ls[:1]))
+            ends.add(hs, ls)
             csum = csum + hs.sum() + ls.sum()
             n += m
             if self.out:
-                at, items = 0, []
-                for p in range(pa, pb):
-                    items.append((p, recs[at:at + int(sizes[p])]))
-                    at += int(sizes[p])
-                self._write_parts(ctx, items)
+                self._write_group(ctx, recs, sizes, pa, pb)
             del recs, hs, ls
-        if first is None:
+        if ends.first is None:
             return 0, None
-        return n, torch.cat([bad.reshape(1), csum.reshape(1), first[0], first[1], last[0],
-                             last[1]])
+        return n, ends.stats(bad, csum)
 
     def _agree_parts(self, comm, outs, nparts):
         """R and the splitters, agreed by every rank (a rank may have run no map;
@@ -626,6 +629,7 @@ class TeraSortSplitJob(SplitJob):
                 if self.sorted_runs:
                     perm, _hs, _ls = S.sort_keys(h, lw)
                     perms.append(perm + at)
+                    del h, lw, _hs, _ls     # the keys are not sent: free them before the gather
                 splits.append(sp)
                 rowsl.append(rw)
                 at += counts[d]
@@ -806,87 +810,20 @@ class TeraSortSplitJob(SplitJob):
     def _reduce_shuffle(self, ctx, outs, offs, nparts, dev):
         """world > 1: every rank gathers the records of each destination's
         partition range from its splits (one pass), one all-to-all-v over
-        RCCL/xGMI, then sorts what it received (its contiguous key range)."""
+        RCCL/xGMI, then sorts what it received (its contiguous key range) or
+        merges the sorted runs.  Every rank takes part in every collective,
+        whether or not it ran maps."""
         comm = ctx.comm
         W, me = comm.world_size, comm.rank
-        # a rank that ran no map learns R (and the splitters) from its peers
-        nparts = max(int(g[0]) for g in comm.all_gather(
-            torch.tensor([nparts or 0], dtype=torch.int64)))
-        # ... and the splitters, which a rank owning several partitions needs to
-        # cut its output (every rank takes part: the collective sequence must
-        # not depend on whether a rank ran maps)
-        spl = None
-        if nparts > 1:
-            k = nparts - 1
-            mine = torch.zeros(1 + 2 * k, dtype=torch.int64)
-            if outs:
-                shi, slo = _parse_keys(self._splitters_of(outs))
-                assert shi.numel() == k, (shi.numel(), k)
-                mine[0] = 1
-                mine[1:1 + k] = shi
-                mine[1 + k:] = slo
-            for g in comm.all_gather(mine):
-                g = g.cpu()
-                if int(g[0]):
-                    spl = (g[1:1 + k], g[1 + k:])
-                    break
-        counts = [0] * W
-        splits, rowsl, perms = [], [], []
-        if outs:
-            his = [o["hi"] for o in outs]
-            los = [o["lo"] for o in outs]
-            rows = [o["row"] for o in outs]
-            bases = [o["records"] for o in outs]
-            at = 0
-            for d in range(W):
-                a, b = self.owner_range(d, W, nparts)
-                starts = offs[:, a]
-                lens = offs[:, b] - offs[:, a]
-                counts[d] = int(lens.sum())
-                if counts[d]:
-                    h, lw, sp, rw = S.tera_collect(his, los, rows, starts, lens,
-                                                   with_keys=self.sorted_runs)
-                    if self.sorted_runs:
-                        perm, _hs, _ls = S.sort_keys(h, lw)
-                        perms.append(perm + at)
-                        del h, lw, _hs, _ls
-                    splits.append(sp)
-                    rowsl.append(rw)
-                    at += counts[d]
-            if splits:
-                send = S.gather_records_multi(bases, torch.cat(splits), torch.cat(rowsl),
-                                              torch.cat(perms) if perms else None)
-            else:
-                send = torch.empty(0, S.RECORD, dtype=torch.uint8, device=dev)
-            del splits, rowsl, perms
-        else:
-            send = torch.empty(0, S.RECORD, dtype=torch.uint8, device=dev)
+        nparts, spl = self._agree_parts(comm, outs, nparts)
+        send, counts = self._send_buffer(outs, offs, nparts, W, dev)
         recv, rcounts = comm.all_to_all_v(send, counts)
         del send
-        if recv.shape[0] == 0:
-            return 0, None
-        if self.sorted_runs:
+        if self.sorted_runs and recv.shape[0]:
             srt, hs, ls = self._merge_received(recv, rcounts)
-        else:
-            srt, hs, ls = S.sort_records(recv)
-        del recv
-        n = int(srt.shape[0])
-        st = torch.cat([S.count_unsorted_dev(hs, ls).reshape(1),
-                        (hs.sum() + ls.sum()).reshape(1), hs[:1], ls[:1], hs[-1:], ls[-1:]])
-        if self.out:
-            a, b = self.owner_range(me, W, nparts)
-            if b - a > 1:
-                if spl is None:
-                    raise RuntimeError("no rank holds the splitters of this job")
-                shi, slo = spl
-                cut = S.split_offsets(hs, ls, shi[a:b - 1].to(dev), slo[a:b - 1].to(dev)) \
-                    .to("cpu").tolist()
-                cut = [0] + cut[1:-1] + [n]
-            else:
-                cut = [0, n]
-            self._write_parts(ctx, [(p, srt[cut[i]:cut[i + 1]])
-                                    for i, p in enumerate(range(a, b))])
-        return n, st
+            del recv
+            return self._owned_stats(ctx, srt, hs, ls, spl, nparts, W, me, dev)
+        return self._sort_received(ctx, recv, spl, nparts, W, me, dev)
 
     @staticmethod
     def _merge_received(recv, rcounts):
@@ -920,9 +857,6 @@ class TeraSortSplitJob(SplitJob):
         ctx.tera_out = (com, attempt, com.work_path(self.conf, attempt),
                         _PartWriter(dev, self.conf.get_boolean("terasort.final.sync", True),
                                     self.conf.get_int("hbmr.terasort.output.writers", 16)))
-
-    def _write_part(self, ctx, p, recs):
-        self._write_parts(ctx, [(p, recs)])
 
     def _write_parts(self, ctx, items):
         """Partitions [(p, records)] that are ready together (one sort group)

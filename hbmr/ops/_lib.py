@@ -121,8 +121,6 @@ _SIGS = {
     "hbmr_split_offsets": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int,
                                    c_void_p, c_void_p]),
     "hbmr_check_sorted": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
-    "hbmr_tera_keys_part": (c_int, [c_void_p, c_long, c_int, c_void_p, c_void_p, c_int, c_void_p,
-                                    c_void_p, c_void_p, c_void_p]),
     "hbmr_tera_collect": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "hbmr_tera_collect_slots": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_long,

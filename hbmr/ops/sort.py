@@ -1,4 +1,4 @@
-"""GPU sort / shuffle primitives (native/kernels/sort.hip) and their CPU twins.
+"""GPU sort / shuffle primitives (native/kernels/sort.hip, sort/*.h) and their CPU twins.
 
 * :func:`radix_sort_pairs` — stable LSD radix sort of uint64 keys (held in
   int64 tensors, compared unsigned) carrying uint32 values.
@@ -12,7 +12,6 @@ the native library must load (no silent fallback).
 from __future__ import annotations
 
 import ctypes
-import os
 
 import numpy as np
 import torch
@@ -21,14 +20,10 @@ from . import _lib
 
 RECORD = 100
 KEY = 10
-# HBMR_TERA_SORT80=1: always the full 10-pass 80-bit key sort (A/B of the
-# hi-only sort + tie fix-up)
-_SORT80 = __import__("os").environ.get("HBMR_TERA_SORT80") == "1"
-
 
 # TeraSort reduce v4: the radix sort covers hi >> TIE_SHIFT (the low bits of hi
-# and lo are ordered by the in-place tie fix); HBMR_TERA_TIE_SHIFT overrides
-TIE_SHIFT = int(os.environ.get("HBMR_TERA_TIE_SHIFT", "16"))
+# and lo are ordered by the in-place tie fix)
+TIE_SHIFT = 16
 # bits of hi the v4 reduce radix-sorts below a group's common key prefix (the
 # group is a key range: its splitters fix the top bits).  40 = 5 passes of 8
 # bits: equal 40-bit prefixes come in pairs or triples among the ~2.5e8 keys of
@@ -37,7 +32,7 @@ TIE_SHIFT = int(os.environ.get("HBMR_TERA_TIE_SHIFT", "16"))
 # (profiles/r05_terasort_1gpu.json).  A 32-bit window leaves runs of equal
 # prefixes longer than the tie fix takes and the group falls back to the
 # full-key path: 0.76 s (profiles/r03_terasort_window.json)
-SORT_BITS = int(os.environ.get("HBMR_TERA_SORT_BITS", "40"))
+SORT_BITS = 40
 
 
 def sort_window(hi_range=None):
@@ -46,11 +41,12 @@ def sort_window(hi_range=None):
     unsigned ints): the bits above their highest differing bit are the same in
     every key of the group, so the sort takes the SORT_BITS below that (ties on
     the sorted prefix are ordered by the full key afterwards)."""
-    if hi_range is None or SORT_BITS <= 0:
+    if hi_range is None:
         return TIE_SHIFT, 64
     lo, up = hi_range
     end = max(8, min(64, (int(lo) ^ int(up)).bit_length()))
     return max(0, end - SORT_BITS), end
+
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
@@ -61,6 +57,15 @@ def _on_gpu(t):
 
 
 # --------------------------------------------------------------------------- radix sort
+def _window_order_np(keys: torch.Tensor, begin_bit: int, end_bit: int):
+    """CPU twin of both radix sorts: (keys as uint64, their stable order by
+    bits [begin_bit, end_bit))."""
+    k = keys.numpy().view(np.uint64)
+    w = end_bit - begin_bit
+    mask = np.uint64((1 << w) - 1 if w < 64 else 0xFFFFFFFFFFFFFFFF)
+    return k, np.argsort((k >> np.uint64(begin_bit)) & mask, kind="stable")
+
+
 def radix_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, begin_bit: int = 0,
                      end_bit: int = 64, stream=None) -> None:
     """In place: sort ``keys`` (int64 storage of uint64) and permute ``vals`` (int32)
@@ -71,11 +76,7 @@ def radix_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, begin_bit: int = 0,
     if n <= 1:
         return
     if not _on_gpu(keys):
-        k = keys.numpy().view(np.uint64)
-        mask = np.uint64(((1 << (end_bit - begin_bit)) - 1) if end_bit - begin_bit < 64
-                         else 0xFFFFFFFFFFFFFFFF)
-        dig = (k >> np.uint64(begin_bit)) & mask
-        order = np.argsort(dig, kind="stable")
+        k, order = _window_order_np(keys, begin_bit, end_bit)
         keys.copy_(torch.from_numpy(k[order].view(np.int64).copy()))
         vals.copy_(vals[torch.from_numpy(order)])
         return
@@ -121,10 +122,7 @@ def radix_sort_keys(keys: torch.Tensor, begin_bit: int = 0, end_bit: int = 64, s
     if n <= 1:
         return keys
     if not _on_gpu(keys):
-        k = keys.numpy().view(np.uint64)
-        w = end_bit - begin_bit
-        mask = np.uint64((1 << w) - 1 if w < 64 else 0xFFFFFFFFFFFFFFFF)
-        order = np.argsort((k >> np.uint64(begin_bit)) & mask, kind="stable")
+        k, order = _window_order_np(keys, begin_bit, end_bit)
         keys.copy_(torch.from_numpy(k[order].view(np.int64).copy()))
         return keys
     if n >= ONESWEEP_MAX:
@@ -143,14 +141,6 @@ def radix_sort_keys(keys: torch.Tensor, begin_bit: int = 0, end_bit: int = 64, s
     _lib.check(rc, "hbmr_radix_sort_keys_u64")
     passes = (end_bit - begin_bit + 7) // 8
     return tk if (not inplace and passes % 2) else keys
-
-
-def argsort_u64(keys: torch.Tensor, stream=None):
-    """(sorted keys, int32 permutation) without modifying ``keys``."""
-    k = keys.clone()
-    v = torch.arange(keys.numel(), dtype=torch.int32, device=keys.device)
-    radix_sort_pairs(k, v, stream=stream)
-    return k, v
 
 
 # --------------------------------------------------------------------------- TeraGen
@@ -195,15 +185,7 @@ def teragen_cpu(first_row: int, nrows: int) -> np.ndarray:
     """Reference TeraGen (TeraGen.java RandomGenerator / SortGenMapper) → uint8 [n, 100]."""
     rows = np.arange(first_row, first_row + nrows, dtype=np.int64)
     out = np.empty((nrows, RECORD), dtype=np.uint8)
-    s = _lcg_jump_np(rows.astype(np.uint64) * np.uint64(3))
-    kb = np.empty((nrows, 12), dtype=np.uint8)
-    for q in range(3):
-        s = (np.uint64(_A) * s + np.uint64(_C)) & np.uint64(_M)
-        temp = s // np.uint64(52)
-        for pos in (3, 2, 1, 0):
-            kb[:, pos + 4 * q] = (32 + temp % np.uint64(95)).astype(np.uint8)
-            temp = temp // np.uint64(95)
-    out[:, :10] = kb[:, :10]
+    out[:, :10] = teragen_keys_cpu(first_row, nrows)
     rid = rows.astype(np.int32)   # Java (int) rowId
     for i in range(nrows):
         t = str(int(rid[i])).encode()[:10]
@@ -257,6 +239,17 @@ def gather_records(records: torch.Tensor, perm: torch.Tensor, stream=None) -> to
     return out
 
 
+def gather_u64(src: torch.Tensor, perm: torch.Tensor, stream=None) -> torch.Tensor:
+    """dst[i] = src[perm[i]] for int64 storage (perm int32)."""
+    if not _on_gpu(src):
+        return src[perm.long()]
+    dst = torch.empty(perm.numel(), dtype=src.dtype, device=src.device)
+    rc = _lib.load().hbmr_gather_u64(_ptr(src), _ptr(perm), perm.numel(), _ptr(dst),
+                                      _lib.stream_handle(stream))
+    _lib.check(rc, "hbmr_gather_u64")
+    return dst
+
+
 def sort_keys(hi: torch.Tensor, lo: torch.Tensor, stream=None):
     """Permutation ordering records by (hi, lo) unsigned; returns (perm, hi_sorted, lo_sorted)."""
     n = hi.numel()
@@ -266,36 +259,27 @@ def sort_keys(hi: torch.Tensor, lo: torch.Tensor, stream=None):
         order = np.lexsort((lw, h)).astype(np.int32)
         return (torch.from_numpy(order), torch.from_numpy(h[order].view(np.int64).copy()),
                 torch.from_numpy(lw[order].view(np.int64).copy()))
-    lib = _lib.load()
-    if not _SORT80:
-        # 8 passes over hi only, lo gathered, then runs of equal hi (rare: hi
-        # holds 8 of the 10 key bytes) ordered by lo in place; a run longer
-        # than the fix-up handles falls back to the full 80-bit sort below
-        perm = torch.arange(n, dtype=torch.int32, device=hi.device)
-        hi_k = hi.clone()
-        radix_sort_pairs(hi_k, perm, 0, 64, stream=stream)
-        lo_s = torch.empty_like(lo)
-        rc = lib.hbmr_gather_u64(_ptr(lo), _ptr(perm), n, _ptr(lo_s), _lib.stream_handle(stream))
-        _lib.check(rc, "hbmr_gather_u64")
-        flag = torch.zeros(1, dtype=torch.int32, device=hi.device)
-        rc = lib.hbmr_tera_tie_fix(_ptr(hi_k), _ptr(lo_s), _ptr(perm), n, _ptr(flag),
-                                   _lib.stream_handle(stream))
-        _lib.check(rc, "hbmr_tera_tie_fix")
-        if not int(flag.item()):
-            return perm, hi_k, lo_s
-        del perm, hi_k, lo_s
+    # 8 passes over hi only, lo gathered, then runs of equal hi (rare: hi
+    # holds 8 of the 10 key bytes) ordered by lo in place; a run longer
+    # than the fix-up handles falls back to the full 80-bit sort below
+    perm = torch.arange(n, dtype=torch.int32, device=hi.device)
+    hi_k = hi.clone()
+    radix_sort_pairs(hi_k, perm, 0, 64, stream=stream)
+    lo_s = gather_u64(lo, perm, stream=stream)
+    flag = torch.zeros(1, dtype=torch.int32, device=hi.device)
+    rc = _lib.load().hbmr_tera_tie_fix(_ptr(hi_k), _ptr(lo_s), _ptr(perm), n, _ptr(flag),
+                                       _lib.stream_handle(stream))
+    _lib.check(rc, "hbmr_tera_tie_fix")
+    if not int(flag.item()):
+        return perm, hi_k, lo_s
+    del perm, hi_k, lo_s
     # LSD: 2 passes over the low 16 bits, then 8 over the high 64 (stable)
     lo_k = lo.clone()
     perm = torch.arange(n, dtype=torch.int32, device=hi.device)
     radix_sort_pairs(lo_k, perm, 0, 16, stream=stream)
-    hi_k = torch.empty_like(hi)
-    rc = lib.hbmr_gather_u64(_ptr(hi), _ptr(perm), n, _ptr(hi_k), _lib.stream_handle(stream))
-    _lib.check(rc, "hbmr_gather_u64")
+    hi_k = gather_u64(hi, perm, stream=stream)
     radix_sort_pairs(hi_k, perm, 0, 64, stream=stream)
-    lo_s = torch.empty_like(lo)
-    rc = lib.hbmr_gather_u64(_ptr(lo), _ptr(perm), n, _ptr(lo_s), _lib.stream_handle(stream))
-    _lib.check(rc, "hbmr_gather_u64")
-    return perm, hi_k, lo_s
+    return perm, hi_k, gather_u64(lo, perm, stream=stream)
 
 
 def sort_records(records: torch.Tensor, stream=None):
@@ -335,50 +319,38 @@ def split_offsets(hi: torch.Tensor, lo: torch.Tensor, split_hi: torch.Tensor,
     return out
 
 
-def count_unsorted(hi: torch.Tensor, lo: torch.Tensor, stream=None) -> int:
-    """Number of adjacent out-of-order key pairs (TeraValidate's check)."""
+def count_unsorted_dev(hi: torch.Tensor, lo: torch.Tensor, stream=None) -> torch.Tensor:
+    """Number of adjacent out-of-order key pairs (TeraValidate's check) as a
+    0-d int64 tensor on the keys' device (no host sync)."""
     n = hi.numel()
     if n <= 1:
-        return 0
+        return torch.zeros((), dtype=torch.int64, device=hi.device)
     if not _on_gpu(hi):
         h = hi.numpy().view(np.uint64)
         lw = lo.numpy().view(np.uint64)
         bad = (h[:-1] > h[1:]) | ((h[:-1] == h[1:]) & (lw[:-1] > lw[1:]))
-        return int(bad.sum())
+        return torch.tensor(int(bad.sum()), dtype=torch.int64)
     bad = torch.zeros(1, dtype=torch.int64, device=hi.device)
     rc = _lib.load().hbmr_check_sorted(_ptr(hi), _ptr(lo), n, _ptr(bad),
                                         _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_check_sorted")
-    return int(bad.item())
+    return bad[0]
 
 
-def keys_from_bytes(keys: list) -> tuple[torch.Tensor, torch.Tensor]:
-    """10-byte keys (bytes) → (hi, lo) int64 tensors (host)."""
-    hi = np.array([int.from_bytes(k[:8].ljust(8, b"\0"), "big") for k in keys], dtype=np.uint64)
-    lo = np.array([int.from_bytes(k[8:10].ljust(2, b"\0"), "big") for k in keys], dtype=np.uint64)
-    return torch.from_numpy(hi.view(np.int64)), torch.from_numpy(lo.view(np.int64))
+def count_unsorted(hi: torch.Tensor, lo: torch.Tensor, stream=None) -> int:
+    """count_unsorted_dev, read back to the host."""
+    return int(count_unsorted_dev(hi, lo, stream=stream))
 
 
 # --------------------------------------------------------------------------- range-partitioned TeraSort
-def tera_keys_part(records: torch.Tensor, split_hi: torch.Tensor, split_lo: torch.Tensor,
-                   stream=None):
+def tera_keys_part(records: torch.Tensor, split_hi: torch.Tensor, split_lo: torch.Tensor):
     """(hi, lo, pid) of every record: key words and its range partition (the
-    number of splitters <= key; splitters sorted, at most 4096)."""
-    n, stride = records.shape
-    ns = split_hi.numel()
+    number of splitters <= key; splitters sorted).  CPU only: the twin that
+    CPU :func:`tera_partition` is built on and the reference its GPU form is
+    tested against."""
     if _on_gpu(records):
-        if ns > 4096:
-            raise ValueError("at most 4096 splitters (4097 partitions)")
-        hi = torch.empty(n, dtype=torch.int64, device=records.device)
-        lo = torch.empty(n, dtype=torch.int64, device=records.device)
-        pid = torch.empty(n, dtype=torch.int64, device=records.device)
-        sh = split_hi.to(records.device)
-        sl = split_lo.to(records.device)
-        rc = _lib.load().hbmr_tera_keys_part(_ptr(records), n, stride, _ptr(sh) if ns else None,
-                                              _ptr(sl) if ns else None, ns, _ptr(hi), _ptr(lo),
-                                              _ptr(pid), _lib.stream_handle(stream))
-        _lib.check(rc, "hbmr_tera_keys_part")
-        return hi, lo, pid
+        raise ValueError("tera_keys_part is the CPU twin: tera_partition runs on the GPU")
+    ns = split_hi.numel()
     hi, lo = tera_keys(records)
     h = hi.numpy().view(np.uint64)
     lw = lo.numpy().view(np.uint64)
@@ -518,6 +490,14 @@ def _ptr_table(ts, device):
     return tab
 
 
+def _piece_meta(starts, lens, device):
+    """One upload for a collect kernel: the S piece starts, then the S + 1
+    prefix sums of the piece lengths (the second pointer is 8 * S bytes in)."""
+    prefix = np.zeros(len(lens) + 1, dtype=np.int64)
+    np.cumsum(np.asarray(lens, dtype=np.int64), out=prefix[1:])
+    return _h2d_i64(np.concatenate([np.asarray(starts, dtype=np.int64), prefix]), device)
+
+
 def tera_collect(his, los, rows, starts, lens, with_keys=True, stream=None):
     """Concatenate pieces [starts[s], starts[s]+lens[s]) of per-split (hi, lo,
     row) arrays → (hi, lo, split, row) (hi/lo None unless ``with_keys``)."""
@@ -532,9 +512,7 @@ def tera_collect(his, los, rows, starts, lens, with_keys=True, stream=None):
             return None, None, split, row
         return (torch.cat([h[sl] for h, sl in zip(his, sel)]),
                 torch.cat([lw[sl] for lw, sl in zip(los, sel)]), split, row)
-    prefix = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum(np.asarray(lens, dtype=np.int64), out=prefix[1:])
-    meta = _h2d_i64(np.concatenate([np.asarray(starts, dtype=np.int64), prefix]), dev)
+    meta = _piece_meta(starts, lens, dev)
     split = torch.empty(n, dtype=torch.int32, device=dev)
     row = torch.empty(n, dtype=torch.int32, device=dev)
     ohi = torch.empty(n, dtype=torch.int64, device=dev) if with_keys else None
@@ -647,9 +625,7 @@ def tera_collect_gid(his, rows, starts, lens, stream=None, window: KeyWindow | N
         w = window.apply_np(hi.numpy().view(np.uint64)) & np.uint64(0xFFFFFFFF)
         pk = (w << np.uint64(32)) | gid.numpy().view(np.uint32).astype(np.uint64)
         return torch.from_numpy(pk.view(np.int64).copy()), None
-    prefix = np.zeros(S + 1, dtype=np.int64)
-    np.cumsum(np.asarray(lens, dtype=np.int64), out=prefix[1:])
-    meta = _h2d_i64(np.concatenate([np.asarray(starts, dtype=np.int64), prefix]), dev)
+    meta = _piece_meta(starts, lens, dev)
     ohi = torch.empty(n, dtype=torch.int64, device=dev)
     gid = None if window is not None else torch.empty(n, dtype=torch.int32, device=dev)
     th, tr = _ptr_table(his, dev), _ptr_table(rows, dev)
@@ -800,29 +776,6 @@ def gather_records_multi(bases, split: torch.Tensor, row: torch.Tensor, perm=Non
                                                 _ptr(res), _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_gather_records_multi")
     return res
-
-
-def gather_u64(src: torch.Tensor, perm: torch.Tensor, stream=None) -> torch.Tensor:
-    """dst[i] = src[perm[i]] for int64 storage (perm int32)."""
-    if not _on_gpu(src):
-        return src[perm.long()]
-    dst = torch.empty(perm.numel(), dtype=src.dtype, device=src.device)
-    rc = _lib.load().hbmr_gather_u64(_ptr(src), _ptr(perm), perm.numel(), _ptr(dst),
-                                      _lib.stream_handle(stream))
-    _lib.check(rc, "hbmr_gather_u64")
-    return dst
-
-
-def count_unsorted_dev(hi: torch.Tensor, lo: torch.Tensor, stream=None) -> torch.Tensor:
-    """count_unsorted as a 0-d int64 device tensor (no host sync)."""
-    n = hi.numel()
-    if n <= 1 or not _on_gpu(hi):
-        return torch.tensor(count_unsorted(hi, lo), dtype=torch.int64, device=hi.device)
-    bad = torch.zeros(1, dtype=torch.int64, device=hi.device)
-    rc = _lib.load().hbmr_check_sorted(_ptr(hi), _ptr(lo), n, _ptr(bad),
-                                        _lib.stream_handle(stream))
-    _lib.check(rc, "hbmr_check_sorted")
-    return bad[0]
 
 
 _SIGN = -0x8000000000000000

@@ -181,6 +181,23 @@ def test_partition_ops_cpu():
     assert pid.tolist() == [sum(1 for s_ in spl if s_ <= k) for k in keys]
 
 
+@pytest.mark.parametrize("sizes,limit,want", [
+    ([5, 20, 3, 4], 10, [(0, 1), (1, 2), (2, 4)]),      # 20 > limit: a group of its own
+    ([0, 0, 4, 0, 6, 0], 10, [(0, 6)]),                 # empty partitions join their neighbours
+    ([0, 0, 4, 0, 6, 0], 9, [(0, 4), (4, 6)]),
+    ([3, 0, 2], 0, [(0, 1), (1, 2), (2, 3)]),           # limit 0: one partition per group ...
+    ([0, 0, 0], 0, [(0, 3)]),                           # ... unless nothing is added
+    ([4, 6, 1], 10, [(0, 2), (2, 3)]),                  # 4 + 6 fits exactly
+    ([7], 3, [(0, 1)]),
+    ([], 10, []),
+])
+def test_partition_groups(sizes, limit, want):
+    """Consecutive partitions [pa, pb) of at most ``limit`` records together;
+    a partition is never split, so one above the limit is a group alone."""
+    got = T.TeraSortSplitJob._groups(np.array(sizes, dtype=np.int64), len(sizes), limit)
+    assert got == want
+
+
 def test_terasort_from_teragen_files(tmp_path):
     inp = tmp_path / "in"
     inp.mkdir()
@@ -278,10 +295,17 @@ def test_gpu_partition_collect_and_multi_gather_match_cpu():
     recs = recs_c.cuda()
     sp = T.create_partitions(recs_c.numpy()[::101, :10].copy(), 37)
     shi, slo = (torch.from_numpy(x.view(np.int64)) for x in T._key_words(sp))
-    g = S.tera_keys_part(recs, shi, slo)
+    # per-record (hi, lo, pid) of the GPU partition, scattered back to input
+    # order through row: the pid of a position is the partition holding it
+    hp, lp, row, offs = (t.cpu() for t in S.tera_partition(recs, shi, slo))
+    pid_p = torch.repeat_interleave(torch.arange(offs.numel() - 1), offs[1:] - offs[:-1])
+    assert sorted(row.tolist()) == list(range(n))
+    g = [torch.empty(n, dtype=torch.int64) for _ in range(3)]
+    for dst, src in zip(g, (hp, lp, pid_p)):
+        dst[row.long()] = src
     c = S.tera_keys_part(recs_c, shi, slo)
     for a, b in zip(g, c):
-        assert torch.equal(a.cpu(), b)
+        assert torch.equal(a, b)
     # collect pieces of three "splits" and gather their records
     parts = [recs[:70000], recs[70000:150000], recs[150000:]]
     his = [S.tera_keys(p)[0] for p in parts]
@@ -547,8 +571,8 @@ def test_gpu_terasort_out_of_core(tmp_path):
 def test_gpu_record_gather_pieces_match_cpu(rb):
     """The 16-B-piece record gather (7 lanes per 100-B record; other sizes:
     a last piece of 1-3 words) and its key outputs against the CPU gather,
-    from several base splits at random rows (record sizes below 12 B take the
-    word-per-lane kernel)."""
+    from several base splits at random rows (record sizes below 12 B: one
+    lane per record, a piece of 1-2 words, no key output)."""
     g = torch.Generator().manual_seed(rb)
     bases = [torch.randint(0, 256, (n, rb), generator=g, dtype=torch.uint8) for n in (1000, 37, 4099)]
     split = torch.randint(0, 3, (20000,), generator=g)
