@@ -11,11 +11,16 @@ the same partitioner and reduce count).
 ``make_reduce_side_job`` is the general join for inputs that are not (the
 contrib/data_join approach): MultipleInputs tags every record with its source,
 the reducer groups by key and emits the cross product of the sources' values
-(inner) or pads missing sides (outer)."""
+(inner) or pads missing sides (outer).
+
+``-gpu`` runs the map-side join as the map-only split-level job of
+hbmr/models/join.py (record join kernels on the GPU map slots); a job it does
+not take logs the reason and runs the classic job."""
 from __future__ import annotations
 
 import argparse
 import itertools
+import logging
 
 from ..io.writable import BytesWritable, Text
 from ..mapred import FileOutputFormat, JobClient, JobConf, Mapper, Reducer
@@ -24,6 +29,8 @@ from ..mapred.formats import KeyValueTextInputFormat, SequenceFileInputFormat, \
 from ..mapred.join import CompositeInputFormat, TupleWritable
 from ..mapred.lib.multiple import MultipleInputs
 from ..utils.reflection import load_class
+
+log = logging.getLogger("hbmr.examples.join")
 
 
 def make_job(inputs, out, join_type="inner", reduces=0, conf=None,
@@ -89,9 +96,49 @@ for _i in range(8):   # importable tag mappers for up to 8 sources
     _tagging_mapper(_i)
 
 
+def _join_gpu(inputs, out, join_type, reduces, conf, cluster, kw):
+    """The join as a split job; None if it is not eligible (the reason is logged)."""
+    from ..models import join as J
+    try:
+        gjob = J.gpu_job(inputs, out, join_type, reduces, base=conf, **kw)
+    except ValueError as e:
+        log.warning("%s; running the classic join job", e)
+        return None
+    own = cluster is None
+    if own:
+        import torch
+        from ..mapred.cluster import LocalCluster
+        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
+        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
+    try:
+        rj = cluster.submit_job(gjob)
+        rj.waitForCompletion()
+        if not rj.isSuccessful():
+            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
+    finally:
+        if own:
+            cluster.shutdown()
+    return rj
+
+
+def run(inputs, out, join_type="inner", reduces=0, conf=None, cluster=None, maps=None, gpu=False,
+        **kw):
+    """Run the map-side join; ``gpu``: as the map-only split-level job of
+    hbmr/models/join.py (record join kernels on the GPU map slots), the classic
+    job if it is not eligible (the reason is logged).  ``kw``: in_format,
+    out_format, out_key, out_value as in :func:`make_job`."""
+    rj = _join_gpu(inputs, out, join_type, reduces, conf, cluster, kw) if gpu else None
+    if rj is not None:
+        return rj
+    job = make_job(inputs, out, join_type, reduces, conf, **kw)
+    if maps:
+        job.set_num_map_tasks(maps)
+    return JobClient.runJob(job, cluster=cluster)
+
+
 def main(argv=None, cluster=None):
     """``hbmr examples join [-m maps] [-r reduces] [-inFormat C] [-outFormat C]
-    [-outKey C] [-outValue C] [-joinOp inner|outer|override] in1 in2 ... out``"""
+    [-outKey C] [-outValue C] [-joinOp inner|outer|override] [-gpu] in1 in2 ... out``"""
     ap = argparse.ArgumentParser(prog="hbmr examples join")
     ap.add_argument("-m", type=int, default=None)
     ap.add_argument("-r", type=int, default=0)
@@ -100,6 +147,8 @@ def main(argv=None, cluster=None):
     ap.add_argument("-outKey", default=None)
     ap.add_argument("-outValue", default=None)
     ap.add_argument("-joinOp", default="inner")
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a map-only split-level job (record join kernels on GPU slots)")
     ap.add_argument("paths", nargs="+", help="input1 input2 [...] output")
     a = ap.parse_args(argv)
     if len(a.paths) < 3:
@@ -109,8 +158,5 @@ def main(argv=None, cluster=None):
                      ("outKey", "out_key"), ("outValue", "out_value")):
         if getattr(a, opt):
             kw[key] = load_class(getattr(a, opt))
-    job = make_job(a.paths[:-1], a.paths[-1], a.joinOp, a.r, **kw)
-    if a.m:
-        job.set_num_map_tasks(a.m)
-    rj = JobClient.runJob(job, cluster=cluster)
+    rj = run(a.paths[:-1], a.paths[-1], a.joinOp, a.r, cluster=cluster, maps=a.m, gpu=a.gpu, **kw)
     return 0 if rj.isSuccessful() else 1

@@ -189,6 +189,22 @@ _SIGS = {
     "hbmr_recsort_set_chunk_lanes": (c_int, [c_int]),
     "hbmr_recsort_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    # record join (native/kernels/recjoin.hip)
+    "hbmr_recjoin_heads": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                                   c_void_p]),
+    "hbmr_recjoin_set_two_level": (c_int, [c_int]),
+    "hbmr_recjoin_rank": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
+                                  c_void_p, c_void_p]),
+    "hbmr_recjoin_expand": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_long, c_int, c_void_p, c_long, c_long,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
+    "hbmr_recjoin_frames": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "hbmr_recjoin_copy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
+                                  c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -336,9 +336,10 @@ def set_chunk_lanes(lanes: int) -> None:
     _lib.check(_lib.load().hbmr_recsort_set_chunk_lanes(lanes), "hbmr_recsort_set_chunk_lanes")
 
 
-def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, check=True):
+def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, check=True, out=None):
     """uint8[out_bytes] with frame ``order[i]`` (None: i) of ``data`` copied to
-    offset ``dst_off[i]``; bytes no frame covers are left unset.  ``check``
+    offset ``dst_off[i]``; bytes no frame covers are left unset (``out``: this
+    device buffer of out_bytes, whose other bytes stay as they are).  ``check``
     validates the offsets against both buffers first (one host read)."""
     n = int(dst_off.numel())
     dev = data.device
@@ -361,7 +362,11 @@ def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, chec
         return torch.from_numpy(out)
     lib = _lib.load()
     with _stream_ctx(stream):
-        out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.numel() != out_bytes or out.device != dev or \
+                not out.is_contiguous():
+            raise ValueError("gather_frames: out must be contiguous uint8[out_bytes] on the device")
         if n == 0 or out_bytes == 0:
             return out
         chunk = int(lib.hbmr_recsort_chunk_bytes())

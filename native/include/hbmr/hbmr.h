@@ -262,6 +262,34 @@ int hbmr_recsort_gather(const uint8_t* src, const uint32_t* perm, const int64_t*
                         const int64_t* flen, const int64_t* dst_off, const int64_t* chunk_base,
                         const uint32_t* chunk_entry, long n, long nchunks, uint8_t* dst,
                         hipStream_t st);
+// ---- record join (native/kernels/recjoin.hip) --------------------------------
+// Sorted splits in recsort's form.  head[i] = 1 if record i opens a group of equal
+// keys; *bad = the first record whose key is below its predecessor's (else ~0)
+int hbmr_recjoin_heads(const uint8_t* data, const int64_t* koff, const int64_t* klen, long n,
+                       int32_t* head, uint32_t* bad, hipStream_t st);
+int hbmr_recjoin_set_two_level(int on);
+// lb[g], eq[g]: lower bound of probe head g's key among the other source's heads
+// (thk: their round keys 0) and whether the head there has the same key
+int hbmr_recjoin_rank(const uint8_t* pdata, const int64_t* pkoff, const int64_t* pklen,
+                      const int32_t* prec, long np, const uint8_t* tdata, const int64_t* tkoff,
+                      const int64_t* tklen, const int32_t* trec, const uint64_t* thk, long nt,
+                      int32_t* lb, int32_t* eq, hipStream_t st);
+// tuples [lo, lo + T) of the planned join: key, record per slot, frame length
+int hbmr_recjoin_expand(const int64_t* tab, int S, const int64_t* base, const int32_t* mask,
+                        const int32_t* first, const int32_t* cnt, const int32_t* osrc,
+                        const int32_t* orec, long K, int override_op, const int32_t* hdr_len,
+                        long lo, long T, int32_t* tkey, int32_t* trec, int64_t* tlen,
+                        hipStream_t st);
+// record and tuple headers of the laid-out frames, and the list of pieces to copy
+int hbmr_recjoin_frames(const int64_t* tab, int S, const int32_t* mask, const int32_t* osrc,
+                        const int32_t* orec, int override_op, const int32_t* hdr_len,
+                        const int32_t* hdr_off, const uint8_t* hdr_bytes, long T,
+                        const int32_t* tkey, const int32_t* trec, const int64_t* tlen,
+                        const int64_t* dst_off, uint8_t* dst, int64_t* psrc, int64_t* plen,
+                        int64_t* pdst, hipStream_t st);
+int hbmr_recjoin_copy(const int64_t* psrc, const int64_t* plen, const int64_t* pdst,
+                      const int64_t* chunk_base, const uint32_t* chunk_entry, long nchunks,
+                      uint8_t* dst, hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
