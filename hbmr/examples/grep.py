@@ -18,6 +18,7 @@ from ..io.writable import LongWritable, Text
 from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf
 from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
 from ..mapred.lib.basic import InverseMapper, LongSumReducer, RegexMapper
+from ._gpu import run_gpu_job
 
 log = logging.getLogger("hbmr.examples.grep")
 
@@ -30,34 +31,17 @@ class DecreasingLong:
 
 
 def _search_gpu(inp, out, regex, group, conf, cluster):
-    """The search job as a split job; False if the pattern is not eligible."""
+    """The search job as a split job; None if the pattern is not eligible."""
     from ..models import grep as G
-    try:
-        job = G.gpu_job(inp, out, regex, group, base=conf)
-    except ValueError as e:
-        log.warning("%s; running the classic search job", e)
-        return False
-    own = cluster is None
-    if own:
-        import torch
-        from ..mapred.cluster import LocalCluster
-        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
-        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
-    try:
-        rj = cluster.submit_job(job)
-        rj.waitForCompletion()
-        if not rj.isSuccessful():
-            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
-    finally:
-        if own:
-            cluster.shutdown()
-    return True
+    return run_gpu_job(lambda: G.gpu_job(inp, out, regex, group, base=conf), "search", conf,
+                       cluster, log)
 
 
 def run(inp, out, regex, group=0, conf=None, cluster=None, verbose=False, gpu=False):
     tmp = tempfile.mkdtemp(prefix="grep-temp-")
     try:
-        if not (gpu and _search_gpu(inp, os.path.join(tmp, "out"), regex, group, conf, cluster)):
+        if not gpu or _search_gpu(inp, os.path.join(tmp, "out"), regex, group, conf,
+                                  cluster) is None:
             _search(inp, os.path.join(tmp, "out"), regex, group, conf, cluster, verbose)
         return _sort(os.path.join(tmp, "out"), out, conf, cluster, verbose)
     finally:

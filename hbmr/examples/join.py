@@ -29,6 +29,7 @@ from ..mapred.formats import KeyValueTextInputFormat, SequenceFileInputFormat, \
 from ..mapred.join import CompositeInputFormat, TupleWritable
 from ..mapred.lib.multiple import MultipleInputs
 from ..utils.reflection import load_class
+from ._gpu import run_gpu_job
 
 log = logging.getLogger("hbmr.examples.join")
 
@@ -99,26 +100,8 @@ for _i in range(8):   # importable tag mappers for up to 8 sources
 def _join_gpu(inputs, out, join_type, reduces, conf, cluster, kw):
     """The join as a split job; None if it is not eligible (the reason is logged)."""
     from ..models import join as J
-    try:
-        gjob = J.gpu_job(inputs, out, join_type, reduces, base=conf, **kw)
-    except ValueError as e:
-        log.warning("%s; running the classic join job", e)
-        return None
-    own = cluster is None
-    if own:
-        import torch
-        from ..mapred.cluster import LocalCluster
-        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
-        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
-    try:
-        rj = cluster.submit_job(gjob)
-        rj.waitForCompletion()
-        if not rj.isSuccessful():
-            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
-    finally:
-        if own:
-            cluster.shutdown()
-    return rj
+    return run_gpu_job(lambda: J.gpu_job(inputs, out, join_type, reduces, base=conf, **kw), "join",
+                       conf, cluster, log)
 
 
 def run(inputs, out, join_type="inner", reduces=0, conf=None, cluster=None, maps=None, gpu=False,

@@ -18,6 +18,7 @@ from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf
 from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
 from ..mapred.lib.basic import IdentityMapper, IdentityReducer, InputSampler, TotalOrderPartitioner
 from ..utils.reflection import load_class
+from ._gpu import run_gpu_job
 
 log = logging.getLogger("hbmr.examples.sort")
 
@@ -54,27 +55,9 @@ def _sort_gpu(job, inp, out, reduces, conf, cluster, in_format, out_format):
     """The sort as a split job (partition file and split points of ``job``, the
     classic job already made); None if the input is not eligible."""
     from ..models import sort as S
-    try:
-        gjob = S.gpu_job(inp, out, reduces, job.get("total.order.partitioner.path"), base=conf,
-                         in_format=in_format, out_format=out_format)
-    except ValueError as e:
-        log.warning("%s; running the classic sort job", e)
-        return None
-    own = cluster is None
-    if own:
-        import torch
-        from ..mapred.cluster import LocalCluster
-        gpus = [list(range(torch.cuda.device_count()))] if torch.cuda.is_available() else None
-        cluster = LocalCluster(JobConf(conf), num_trackers=1, gpus=gpus)
-    try:
-        rj = cluster.submit_job(gjob)
-        rj.waitForCompletion()
-        if not rj.isSuccessful():
-            raise RuntimeError(f"Job failed: {rj.getID()} {rj.getFailureInfo()}")
-    finally:
-        if own:
-            cluster.shutdown()
-    return rj
+    return run_gpu_job(
+        lambda: S.gpu_job(inp, out, reduces, job.get("total.order.partitioner.path"), base=conf,
+                          in_format=in_format, out_format=out_format), "sort", conf, cluster, log)
 
 
 def run(inp, out, reduces=1, total_order=None, conf=None, cluster=None, in_format=None,

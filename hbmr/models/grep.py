@@ -19,6 +19,7 @@ from __future__ import annotations
 from ..gpu.splitjob import SplitJob
 from ..io.writable import LongWritable, Text
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
+from . import records
 from .wordcount import WordCountSplitJob
 
 REGEX_KEY = "mapred.mapper.regex"
@@ -83,7 +84,6 @@ class GrepSplitJob(SplitJob):
         return grep.merge_tables(blob, cnt, max(1, ctx.world_size))
 
     def reduce(self, ctx, combined):
-        from ..io import sequencefile as seqf
         from ..mapred import counters as C
         from ..ops import grep, text
         blob, counts, part_bytes, part_words = combined
@@ -93,14 +93,9 @@ class GrepSplitJob(SplitJob):
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_GROUPS, len(items))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, len(items))
         if self.out:
-            import os
-            tmp = os.path.join(self.out, "_temporary")
-            os.makedirs(tmp, exist_ok=True)
-            name = f"part-{ctx.rank:05d}"
-            with seqf.Writer(os.path.join(tmp, name), Text, LongWritable) as w:
+            with records.part_writer(self.out, f"part-{ctx.rank:05d}", Text, LongWritable) as w:
                 for m, n in items:
                     w.append(Text(m), LongWritable(n))
-            os.replace(os.path.join(tmp, name), os.path.join(self.out, name))
         return {"distinct": len(items), "matches": sum(n for _, n in items)}
 
 

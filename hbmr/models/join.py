@@ -17,6 +17,7 @@ import re
 
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import FileOutputFormat, JobConf
+from . import records
 
 OP_KEY = "hbmr.join.op"
 OUT_KEY_CLASS_KEY = "hbmr.join.output.key.class"
@@ -55,19 +56,10 @@ class JoinSplitJob(SplitJob):
         return out
 
     def load_split(self, spec: SplitSpec, device):
-        import torch
-
-        from ..io import sequencefile as seqf
-        from ..ops import recsort
         sources, vclasses = [], []
         for f in spec.params["files"]:
-            data, index = recsort.index_records(f["path"], f["start"], f["length"])
-            data, index = torch.from_numpy(data), torch.from_numpy(index)
-            if str(device) != "cpu":
-                data, index = data.to(device), index.to(device)
-            sources.append((data, index))
-            with seqf.Reader(f["path"]) as r:
-                vclasses.append(r.value_class_name)
+            sources.append(records.load_record_split(f["path"], f["start"], f["length"], device))
+            vclasses.append(records.first_classes([f["path"]])[1])
         return {"sources": sources, "value_classes": vclasses, "part": spec.params["part"],
                 "files": [f["path"] for f in spec.params["files"]]}
 
@@ -83,7 +75,6 @@ class JoinSplitJob(SplitJob):
 
     # -- map --------------------------------------------------------------------------
     def _map(self, ctx, split):
-        from ..io import sequencefile as seqf
         from ..io.writable import class_for_java_name
         from ..mapred import counters as C
         from ..ops import recjoin
@@ -102,12 +93,9 @@ class JoinSplitJob(SplitJob):
                 n = sum(int(ch.flen.size) for ch in recjoin.join_chunks(
                     sources, self.op, headers, self.chunk_bytes, stream))
                 return {"records": n}
-            tmp = os.path.join(self.out, "_temporary")
-            os.makedirs(tmp, exist_ok=True)
-            name = f"part-{split['part']:05d}"
-            with seqf.Writer(os.path.join(tmp, name), self.key_class, self.value_class) as w:
+            with records.part_writer(self.out, f"part-{split['part']:05d}", self.key_class,
+                                     self.value_class) as w:
                 n = recjoin.write_join(w, sources, self.op, headers, self.chunk_bytes, stream)
-            os.replace(os.path.join(tmp, name), os.path.join(self.out, name))
         except recjoin.UnsortedInput as e:
             raise IOError(f"{split['files'][e.source]} is not sorted: the key of record "
                           f"{e.record} is below its predecessor's") from e
@@ -121,11 +109,9 @@ class JoinSplitJob(SplitJob):
         return self._map(ctx, split)
 
     def job_succeeded(self, jip):
-        import shutil
         if self.out:
             os.makedirs(self.out, exist_ok=True)
-            shutil.rmtree(os.path.join(self.out, "_temporary"), ignore_errors=True)
-            open(os.path.join(self.out, "_SUCCESS"), "wb").close()
+            records.finish_output(self.out)
 
 
 def _flat_sources(expr, base):
@@ -153,11 +139,8 @@ def _flat_sources(expr, base):
 def why_ineligible(inputs, join_type="inner", base=None, reduces=0, in_format=None,
                    out_format=None, expr=None):
     """None if GPU Join takes this job, else the reason it does not."""
-    from ..io import sequencefile as seqf
     from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
     from ..mapred.join import CompositeInputFormat
-    from ..ops import recsort
-    from .sort import _input_files
     if base is not None:
         if base.get("mapred.join.keycomparator"):
             return f"custom key comparator {base.get('mapred.join.keycomparator')}"
@@ -183,24 +166,17 @@ def why_ineligible(inputs, join_type="inner", base=None, reduces=0, in_format=No
         return f"custom output format {out_format.__name__}"
     if base is not None and base.get_boolean("mapred.output.compress", False):
         return "compressed output"
-    kclasses, vclasses = set(), set()
+    classes = set()
     for p in paths:
         if not os.path.exists(p):
             return f"input {p} is not a local path"
-        for f in _input_files(p):
-            if not os.path.isfile(f):
-                return f"input {f} is not a local file"
-            with seqf.Reader(f) as r:
-                if r.compression != seqf.NONE:
-                    return f"{r.compression}-compressed input {f}"
-                if r.key_class_name not in recsort.KEY_CLASSES:
-                    return (f"key class {r.key_class_name} of {f} (byte-string keys only: "
-                            "BytesWritable, Text)")
-                kclasses.add(r.key_class_name)
-                vclasses.add(r.value_class_name)
-    if len(kclasses) > 1:
+        for f in records.input_files(p):
+            why = records.file_reason(f, classes)
+            if why is not None:
+                return why
+    if len({k for k, _ in classes}) > 1:
         return "sources of different key classes"
-    if op == "override" and len(vclasses) > 1:
+    if op == "override" and len({v for _, v in classes}) > 1:
         return "override over sources of different value classes"
     return None
 
@@ -210,24 +186,16 @@ def gpu_job(inputs, output, join_type="inner", reduces=0, base=None, in_format=N
     """The join of ``inputs`` (sorted, identically partitioned SequenceFile
     directories) as a map-only split-level job.  Raises ValueError, with the
     reason, for anything not eligible (:func:`why_ineligible`)."""
-    from ..io import sequencefile as seqf
     from ..mapred.formats import SequenceFileInputFormat
     from ..mapred.join import CompositeInputFormat, TupleWritable
     from ..utils.reflection import class_name
-    from .sort import _input_files
     why = why_ineligible(inputs, join_type, base, reduces, in_format, out_format, expr)
     if why is not None:
         raise ValueError(f"join of {list(inputs)!r} is not eligible for the GPU: {why}")
     if expr is None:
         expr = CompositeInputFormat.compose(join_type, SequenceFileInputFormat, *inputs)
     op, paths = _flat_sources(expr, base)
-    kc, vc = "org.apache.hadoop.io.BytesWritable", "org.apache.hadoop.io.BytesWritable"
-    for p in paths:
-        files = _input_files(p)
-        if files:
-            with seqf.Reader(files[0]) as r:
-                kc, vc = r.key_class_name, r.value_class_name
-            break
+    kc, vc = records.first_classes([f for p in paths for f in records.input_files(p)])
     if op != "override":
         vc = TupleWritable.JAVA_NAME
     job = JobConf(base)

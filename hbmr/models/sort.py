@@ -19,10 +19,9 @@ maps either.
 """
 from __future__ import annotations
 
-import os
-
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
+from . import records
 
 KEY_CLASS_KEY = "hbmr.sort.key.class"
 VALUE_CLASS_KEY = "hbmr.sort.value.class"
@@ -85,14 +84,8 @@ class SortSplitJob(SplitJob):
         return out
 
     def load_split(self, spec: SplitSpec, device):
-        import torch
-
-        from ..ops import recsort
         p = spec.params
-        data, index = recsort.index_records(p["path"], p["start"], p["length"])
-        data, index = torch.from_numpy(data), torch.from_numpy(index)
-        if str(device) != "cpu":
-            data, index = data.to(device), index.to(device)
+        data, index = records.load_record_split(p["path"], p["start"], p["length"], device)
         return {"data": data, "index": index}
 
     def load_split_sample(self, spec, device, fraction):
@@ -113,10 +106,10 @@ class SortSplitJob(SplitJob):
         n = int(index.shape[1])
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, n)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        perm, records, nbytes, blob = recsort.sort_records(
+        perm, nrec, nbytes, blob = recsort.sort_records(
             data, index, self.nparts, self.split_points, getattr(ctx, "stream", None))
         meta = _meta(index)[perm.to(index.device).long()]
-        return {"blob": blob, "meta": meta, "records": records, "bytes": nbytes}
+        return {"blob": blob, "meta": meta, "records": nrec, "bytes": nbytes}
 
     def map_gpu(self, ctx, split):
         return self._map(ctx, split)
@@ -152,7 +145,6 @@ class SortSplitJob(SplitJob):
     def reduce(self, ctx, combined):
         import torch
 
-        from ..io import sequencefile as seqf
         from ..mapred import counters as C
         from ..ops import recsort
         blob, meta, send_bytes, send_recs = combined
@@ -162,30 +154,25 @@ class SortSplitJob(SplitJob):
         flen = rmeta[:, 0].contiguous()
         foff = torch.cumsum(flen, 0) - flen
         index = torch.stack([foff, flen, foff + rmeta[:, 1], rmeta[:, 2]]).contiguous()
-        perm, records = recsort.sort_perm(rblob, index, self.nparts, self.split_points)
+        perm, nrec = recsort.sort_perm(rblob, index, self.nparts, self.split_points)
         pa, pb = _owned(ctx.rank, max(1, ctx.world_size), self.nparts)
-        if sum(records[:pa]) or sum(records[pb:]):
+        if sum(nrec[:pa]) or sum(nrec[pb:]):
             raise RuntimeError("records of a partition this rank does not own arrived here")
         written = 0
         if self.out:
-            tmp = os.path.join(self.out, "_temporary")
-            os.makedirs(tmp, exist_ok=True)
             r0 = 0
             for p in range(pa, pb):
-                name = f"part-{p:05d}"
-                with seqf.Writer(os.path.join(tmp, name), self.key_class, self.value_class) as w:
-                    written += recsort.write_part(w, rblob, index, perm[r0:r0 + records[p]])
-                r0 += records[p]
-                os.replace(os.path.join(tmp, name), os.path.join(self.out, name))
+                with records.part_writer(self.out, f"part-{p:05d}", self.key_class,
+                                         self.value_class) as w:
+                    written += recsort.write_part(w, rblob, index, perm[r0:r0 + nrec[p]])
+                r0 += nrec[p]
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_RECORDS, int(perm.numel()))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, written)
         return {"records": written, "parts": pb - pa}
 
     def job_succeeded(self, jip):
-        import shutil
         if self.out:
-            shutil.rmtree(os.path.join(self.out, "_temporary"), ignore_errors=True)
-            open(os.path.join(self.out, "_SUCCESS"), "wb").close()
+            records.finish_output(self.out)
 
 
 def _meta(index):
@@ -195,23 +182,9 @@ def _meta(index):
     return torch.stack([index[1], index[2] - index[0], index[3]], dim=1)
 
 
-def _input_files(inputs):
-    paths = [inputs] if isinstance(inputs, str) else list(inputs)
-    files = []
-    for p in paths:
-        if os.path.isdir(p):
-            files += [os.path.join(p, f) for f in sorted(os.listdir(p))
-                      if not f.startswith(("_", "."))]
-        else:
-            files.append(p)
-    return files
-
-
 def why_ineligible(inputs, base=None, in_format=None, out_format=None):
     """None if GPU Sort takes this job, else the reason it does not."""
-    from ..io import sequencefile as seqf
     from ..mapred.formats import SequenceFileInputFormat, SequenceFileOutputFormat
-    from ..ops import recsort
     if in_format is not None and in_format is not SequenceFileInputFormat:
         return f"custom input format {in_format.__name__}"
     if out_format is not None and out_format is not SequenceFileOutputFormat:
@@ -221,16 +194,10 @@ def why_ineligible(inputs, base=None, in_format=None, out_format=None):
     if base is not None and base.get_boolean("mapred.output.compress", False):
         return "compressed output"
     classes = set()
-    for f in _input_files(inputs):
-        if not os.path.isfile(f):
-            return f"input {f} is not a local file"
-        with seqf.Reader(f) as r:
-            if r.compression != seqf.NONE:
-                return f"{r.compression}-compressed input {f}"
-            if r.key_class_name not in recsort.KEY_CLASSES:
-                return (f"key class {r.key_class_name} of {f} (byte-string keys only: "
-                        "BytesWritable, Text)")
-            classes.add((r.key_class_name, r.value_class_name))
+    for f in records.input_files(inputs):
+        why = records.file_reason(f, classes)
+        if why is not None:
+            return why
     if len(classes) > 1:
         return "inputs of different key/value classes"
     return None
@@ -243,18 +210,13 @@ def gpu_job(inputs, output, reduces=1, partition_file=None, base=None, maps=None
     keys become the split points.  Raises ValueError, with the reason, for
     anything not eligible: RECORD- or BLOCK-compressed input, a key class other
     than BytesWritable or Text, a custom input/output format or comparator."""
-    from ..io import sequencefile as seqf
     why = why_ineligible(inputs, base, in_format, out_format)
     if why is not None:
         raise ValueError(f"sort of {inputs!r} is not eligible for the GPU: {why}")
     job = JobConf(base)
     job.set_job_name("sorter-gpu")
     job.set("hbmr.splitjob.class", "hbmr.models.sort:SortSplitJob")
-    files = _input_files(inputs)
-    kc, vc = "org.apache.hadoop.io.BytesWritable", "org.apache.hadoop.io.BytesWritable"
-    if files:
-        with seqf.Reader(files[0]) as r:
-            kc, vc = r.key_class_name, r.value_class_name
+    kc, vc = records.first_classes(records.input_files(inputs))
     job.set(KEY_CLASS_KEY, kc)
     job.set(VALUE_CLASS_KEY, vc)
     job.set_num_reduce_tasks(max(1, reduces))

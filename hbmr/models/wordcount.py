@@ -325,13 +325,9 @@ class WordCountSplitJob(SplitJob):
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_GROUPS, len(items))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, len(items))
         if self.out:
-            import os
-            tmp = os.path.join(self.out, "_temporary")
-            os.makedirs(tmp, exist_ok=True)
-            name = f"part-{ctx.rank:05d}"
-            with open(os.path.join(tmp, name), "wb") as f:
+            from . import records
+            with records.part_writer(self.out, f"part-{ctx.rank:05d}") as f:
                 f.write(b"".join(w + b"\t" + str(n).encode() + b"\n" for w, n in items))
-            os.replace(os.path.join(tmp, name), os.path.join(self.out, name))
         return {"distinct": len(items), "words": total}
 
     @staticmethod
@@ -368,11 +364,9 @@ class WordCountSplitJob(SplitJob):
         return got_b[0], got_w[0]
 
     def job_succeeded(self, jip):
-        import os
-        import shutil
+        from . import records
         if self.out:
-            shutil.rmtree(os.path.join(self.out, "_temporary"), ignore_errors=True)
-            open(os.path.join(self.out, "_SUCCESS"), "wb").close()
+            records.finish_output(self.out)
 
 
 def gpu_job(inputs, output, base=None, maps=None) -> JobConf:

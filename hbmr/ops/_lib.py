@@ -186,7 +186,6 @@ _SIGS = {
     "hbmr_recsort_cuts": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p,
                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "hbmr_recsort_chunk_bytes": (c_int, []),
-    "hbmr_recsort_set_chunk_lanes": (c_int, [c_int]),
     "hbmr_recsort_gather": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_long, c_long, c_void_p, c_void_p]),
     # record join (native/kernels/recjoin.hip)
@@ -267,6 +266,11 @@ def load():
 def check(rc: int, what: str) -> None:
     if rc != 0:
         raise RuntimeError(f"{what} failed with native error code {rc}")
+
+
+def ptr(t):
+    """Device address of a tensor as an int (None stays None: a null pointer)."""
+    return None if t is None else t.data_ptr()
 
 
 def stream_handle(stream=None) -> int:

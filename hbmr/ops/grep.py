@@ -39,7 +39,6 @@ TABLE_BYTES = 32 << 10                  # the transition table sits in LDS
 MAX_COUNT = 16                          # largest n of {m,n}
 WIDE_CLASS = 64
 INITIAL_TABLE = 1 << 21                 # first match-table size tried (slots)
-_TABLE_MAX = 1 << 28
 
 _ASCII = (1 << 128) - 1
 _NL = 1 << 10
@@ -429,14 +428,6 @@ def merge_tables_cpu(blob: bytes, counts, R: int = 1):
 _ptr, _st, _call = text._ptr, text._st, text._call
 
 
-def _scan(tc):
-    """Exclusive int64 scan of per-tile counts and their total."""
-    base = torch.zeros(tc.numel(), dtype=torch.int64, device=tc.device)
-    csum = torch.cumsum(tc.to(torch.int64), 0)
-    base[1:] = csum[:-1]
-    return base, int(csum[-1])
-
-
 def candidates(buf, prog, stream=None):
     """(pos, len int32, end int64, non_ascii) of every start offset of the
     aligned device buffer with a match, in position order."""
@@ -450,7 +441,7 @@ def candidates(buf, prog, stream=None):
     tc = torch.empty(tiles, dtype=torch.int32, device=dev)
     flag = torch.zeros(1, dtype=torch.int32, device=dev)
     _call("hbmr_grep_cand_count", _ptr(buf), n, *dfa, _ptr(tc), _ptr(flag), _st(stream))
-    base, nc = _scan(tc)
+    base, nc = text._tile_scan(tc)
     pos = torch.empty(nc, dtype=torch.int32, device=dev)
     ln = torch.empty(nc, dtype=torch.int32, device=dev)
     end = torch.empty(nc, dtype=torch.int64, device=dev)
@@ -477,7 +468,7 @@ def select(pos, ln, end, stream=None):
     _call("hbmr_grep_prefix_max", _ptr(end), nc, _ptr(bpre), _ptr(pmax), _st(stream))
     bc = torch.empty(blocks, dtype=torch.int32, device=dev)
     _call("hbmr_grep_select_count", _ptr(pos), _ptr(ln), _ptr(pmax), nc, _ptr(bc), _st(stream))
-    base, ns = _scan(bc)
+    base, ns = text._tile_scan(bc)
     spos = torch.empty(ns, dtype=torch.int32, device=dev)
     slen = torch.empty(ns, dtype=torch.int32, device=dev)
     _call("hbmr_grep_select_write", _ptr(pos), _ptr(ln), _ptr(pmax), nc, _ptr(base), _ptr(spos),
@@ -488,51 +479,14 @@ def select(pos, ln, end, stream=None):
 def aggregate(buf, starts, lens, weights=None, R=1, stream=None):
     """Exact per-span totals: (ustart, ulen, ucount int64, upart int32), unordered.
     ``upart`` = (Text.hashCode() & INT_MAX) % R (Hadoop's HashPartitioner)."""
-    dev = buf.device
-    ns = starts.numel()
-    n = buf.numel()
-    full = min(text._pow2(2 * max(ns, 1)), _TABLE_MAX)
-    cap = min(full, INITIAL_TABLE)
-    while True:
-        tkeys = torch.zeros(cap, dtype=torch.int64, device=dev)
-        tcounts = torch.zeros(cap, dtype=torch.int64, device=dev)
-        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        if ns:
-            _call("hbmr_span_insert", _ptr(buf), n, _ptr(starts), _ptr(lens), _ptr(weights), ns,
-                  _ptr(tkeys), _ptr(tcounts), cap, _ptr(ovf), _st(stream))
-        if int(ovf) == 0:
-            break
-        if cap >= full:
-            raise RuntimeError(f"match table overflow at {cap} slots for {ns} matches")
-        cap = min(cap * 4, full)
-    ustart = torch.empty(min(cap, max(ns, 1)), dtype=torch.int32, device=dev)
-    ulen = torch.empty_like(ustart)
-    ucount = torch.empty(ustart.numel(), dtype=torch.int64, device=dev)
-    upart = torch.empty(ustart.numel(), dtype=torch.int32, device=dev)
-    counter = torch.zeros(1, dtype=torch.int32, device=dev)
-    if ns:
-        _call("hbmr_span_compact", _ptr(buf), _ptr(starts), _ptr(lens), _ptr(tkeys),
-              _ptr(tcounts), cap, int(R), _ptr(ustart), _ptr(ulen), _ptr(ucount), _ptr(upart),
-              _ptr(counter), _st(stream))
-    nu = int(counter)
-    return ustart[:nu], ulen[:nu], ucount[:nu], upart[:nu]
+    compact = ("hbmr_span_compact", _ptr(buf), _ptr(starts), _ptr(lens))
+    return text._aggregate("hbmr_span_insert", compact, ("match", "matches"), INITIAL_TABLE, buf,
+                           starts, lens, weights, R, stream)
 
 
 def lines(blob, stream=None):
     """(start, len) int32 pairs of the ``\\n``-terminated entries of a blob."""
-    n = blob.numel()
-    dev = blob.device
-    tiles = _lib.load().hbmr_wc_tiles(n)
-    if tiles == 0:
-        z = torch.empty(0, dtype=torch.int32, device=dev)
-        return z, z
-    tc = torch.empty(tiles, dtype=torch.int32, device=dev)
-    _call("hbmr_lines_count", _ptr(blob), n, _ptr(tc), _st(stream))
-    base, ne = _scan(tc)
-    starts = torch.empty(ne, dtype=torch.int32, device=dev)
-    lens = torch.empty(ne, dtype=torch.int32, device=dev)
-    _call("hbmr_lines_write", _ptr(blob), n, _ptr(base), _ptr(starts), _ptr(lens), _st(stream))
-    return starts, lens
+    return text._itemize("hbmr_lines_count", "hbmr_lines_write", blob, stream)
 
 
 def count_matches(buf: torch.Tensor, prog: GrepProgram, stream=None):
@@ -559,16 +513,5 @@ def merge_tables(blob: torch.Tensor, counts: torch.Tensor, R: int = 1, stream=No
     ``\\n`` only.  Returns (blob, counts, part_bytes, part_words)."""
     if blob.device.type != "cuda":
         return merge_tables_cpu(bytes(blob.numpy()), counts, R)
-    blob = text._aligned(blob.contiguous())
-    starts, lens = lines(blob, stream)
-    if starts.numel() != counts.numel():
-        raise ValueError(f"match table mismatch: {starts.numel()} entries, "
-                         f"{counts.numel()} counts")
-    us, ul, uc, up = aggregate(blob, starts, lens, counts.contiguous(), R, stream)
-    order = torch.argsort(up, stable=True)
-    out = text.pack(blob, us, ul, order, stream)
-    up_o = up[order].to(torch.int64)
-    part_words = torch.bincount(up_o, minlength=R)
-    part_bytes = torch.bincount(up_o, weights=(ul[order].to(torch.float64) + 1),
-                                minlength=R).to(torch.int64)
-    return out, uc[order], part_bytes.tolist(), part_words.tolist()
+    return text._merge(lines, aggregate, ("match", "entries"), text._aligned(blob.contiguous()),
+                       counts, R, stream)

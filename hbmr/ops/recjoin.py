@@ -425,15 +425,9 @@ class _Emitter:
     def copy(self, pieces, out):
         """The piece copy into ``out``: chunk table, then one launch."""
         psrc, plen, pdst = pieces
-        P = int(plen.numel())
         with _stream_ctx(self.stream):
-            nch = torch.where(plen > 0, (((pdst + out.data_ptr()) & 15) + plen + 255) // 256, 0)
-            cbase = torch.zeros(P + 1, dtype=torch.int64, device=self.dev)
-            torch.cumsum(nch, 0, out=cbase[1:])
-            total = int(cbase[-1].item())
+            cbase, entry, total = recsort._chunk_table(pdst, plen, out, skip_empty=True)
             if total:
-                entry = torch.repeat_interleave(
-                    torch.arange(P, dtype=torch.int32, device=self.dev), nch, output_size=total)
                 rc = _lib.load().hbmr_recjoin_copy(_ptr(psrc), _ptr(plen), _ptr(pdst), _ptr(cbase),
                                                    _ptr(entry), total, _ptr(out),
                                                    _lib.stream_handle(self.stream))

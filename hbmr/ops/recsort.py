@@ -32,9 +32,6 @@ from . import sort as _sort
 FOFF, FLEN, KOFF, KLEN = range(4)
 KEY_CLASSES = ("org.apache.hadoop.io.BytesWritable", "org.apache.hadoop.io.Text")
 SYNC_SIZE = 20
-# the frame gather finds a chunk's record through a chunk → record table (one
-# load) instead of a binary search over the chunk offsets per chunk (A/B knob)
-CHUNK_MAP = True
 
 _CPU_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "lib",
                          "libhbmr_cpu.so")
@@ -205,8 +202,7 @@ def sort_records_cpu(data, index, nparts, split_points=None):
 
 
 # --------------------------------------------------------------------------- device
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr
 
 
 def _stream_ctx(stream):
@@ -326,14 +322,24 @@ def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None):
     return perm, part_records
 
 
-def chunk_lanes() -> int:
-    return int(_lib.load().hbmr_recsort_chunk_bytes()) // 16
-
-
-def set_chunk_lanes(lanes: int) -> None:
-    """Lanes that share one chunk of the frame gather (16, 32 or 64): an A/B
-    knob of tools/bench_recsort.py."""
-    _lib.check(_lib.load().hbmr_recsort_set_chunk_lanes(lanes), "hbmr_recsort_set_chunk_lanes")
+def _chunk_table(dst_off, lens, out, skip_empty=False):
+    """(base int64[n + 1], entry int32[total], total): the chunk table of a copy
+    of n runs of ``lens`` bytes to the offsets ``dst_off`` of ``out``.  A run is
+    cut into chunks of hbmr_recsort_chunk_bytes() bytes counted from the 16-byte
+    boundary below its first byte in memory; ``base`` is the exclusive scan of
+    the chunks per run, ``entry`` the run of each chunk.  ``skip_empty``: an
+    empty run gets no chunk (else one if it starts off a boundary)."""
+    chunk = int(_lib.load().hbmr_recsort_chunk_bytes())
+    n = int(lens.numel())
+    nch = (((dst_off + out.data_ptr()) & 15) + lens + (chunk - 1)) // chunk
+    if skip_empty:
+        nch = torch.where(lens > 0, nch, 0)
+    base = torch.zeros(n + 1, dtype=torch.int64, device=out.device)
+    torch.cumsum(nch, 0, out=base[1:])
+    total = int(base[-1].item())
+    entry = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=out.device), nch,
+                                    output_size=total)
+    return base, entry, total
 
 
 def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, check=True, out=None):
@@ -369,15 +375,7 @@ def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, chec
             raise ValueError("gather_frames: out must be contiguous uint8[out_bytes] on the device")
         if n == 0 or out_bytes == 0:
             return out
-        chunk = int(lib.hbmr_recsort_chunk_bytes())
-        nch = (((dst_off + out.data_ptr()) & 15) + lens + (chunk - 1)) // chunk
-        base = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(nch, 0, out=base[1:])
-        total = int(base[-1].item())
-        entry = None
-        if CHUNK_MAP and total:
-            entry = torch.repeat_interleave(torch.arange(n, dtype=torch.int32, device=dev), nch,
-                                            output_size=total)
+        base, entry, total = _chunk_table(dst_off, lens, out)
         rc = lib.hbmr_recsort_gather(_ptr(data), _ptr(order), _ptr(foff), _ptr(flen),
                                      _ptr(dst_off.contiguous()), _ptr(base), _ptr(entry), n, total,
                                      _ptr(out), _lib.stream_handle(stream))

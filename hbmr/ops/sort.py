@@ -48,8 +48,7 @@ def sort_window(hi_range=None):
     return max(0, end - SORT_BITS), end
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr
 
 
 def _on_gpu(t):

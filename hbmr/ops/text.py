@@ -22,8 +22,7 @@ _TABLE_MAX = 1 << 28
 INITIAL_TABLE = 1 << 21     # first word-table size tried (slots)
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
+_ptr = _lib.ptr
 
 
 def _st(stream):
@@ -36,65 +35,83 @@ def _call(name, *args):
 
 
 # --------------------------------------------------------------------------- GPU
-def tokenize(buf: torch.Tensor, stream=None):
-    """Word (start, len) int32 pairs of a uint8 device buffer, in order."""
+def _tile_scan(tc):
+    """Exclusive int64 scan of per-tile counts and their total."""
+    base = torch.zeros(tc.numel(), dtype=torch.int64, device=tc.device)
+    csum = torch.cumsum(tc.to(torch.int64), 0)
+    base[1:] = csum[:-1]
+    return base, int(csum[-1])
+
+
+def _itemize(count, write, buf, stream):
+    """(start, len) int32 pairs of the items of an aligned uint8 device buffer,
+    in order: the count / write kernel pair ``count``, ``write``."""
     n = buf.numel()
     dev = buf.device
-    lib = _lib.load()
-    tiles = lib.hbmr_wc_tiles(n)
+    tiles = _lib.load().hbmr_wc_tiles(n)
     if tiles == 0:
         z = torch.empty(0, dtype=torch.int32, device=dev)
         return z, z
     tc = torch.empty(tiles, dtype=torch.int32, device=dev)
-    _call("hbmr_wc_tokenize_count", _ptr(buf), n, _ptr(tc), _st(stream))
-    base = torch.zeros(tiles, dtype=torch.int64, device=dev)
-    csum = torch.cumsum(tc.to(torch.int64), 0)
-    base[1:] = csum[:-1]
-    nw = int(csum[-1])
-    starts = torch.empty(nw, dtype=torch.int32, device=dev)
-    lens = torch.empty(nw, dtype=torch.int32, device=dev)
-    if nw:
-        _call("hbmr_wc_tokenize_write", _ptr(buf), n, _ptr(base), _ptr(starts), _ptr(lens),
-              _st(stream))
+    _call(count, _ptr(buf), n, _ptr(tc), _st(stream))
+    base, ni = _tile_scan(tc)
+    starts = torch.empty(ni, dtype=torch.int32, device=dev)
+    lens = torch.empty(ni, dtype=torch.int32, device=dev)
+    if ni:
+        _call(write, _ptr(buf), n, _ptr(base), _ptr(starts), _ptr(lens), _st(stream))
     return starts, lens
+
+
+def tokenize(buf: torch.Tensor, stream=None):
+    """Word (start, len) int32 pairs of a uint8 device buffer, in order."""
+    return _itemize("hbmr_wc_tokenize_count", "hbmr_wc_tokenize_write", buf, stream)
 
 
 def _pow2(x):
     return 1 << max(10, int(x - 1).bit_length())
 
 
-def aggregate(buf, starts, lens, weights=None, R=1, stream=None):
-    """Exact per-word totals: (ustart, ulen, ucount int64, upart int32), unordered.
-    ``upart`` = (Text.hashCode() & INT_MAX) % R (Hadoop's HashPartitioner)."""
+def _aggregate(insert, compact, what, initial, buf, starts, lens, weights, R, stream):
+    """Exact per-item totals: (ustart, ulen, ucount int64, upart int32), unordered.
+    ``insert``: the insert entry point; ``compact``: the compact entry point and
+    its arguments ahead of the table; ``what`` = (table, items) as the overflow
+    message names them; ``initial``: the first table size tried (slots)."""
     dev = buf.device
-    nw = starts.numel()
+    ni = starts.numel()
     n = buf.numel()
-    # distinct words are usually far fewer than words: start at ≤ 2M slots
+    # distinct items are usually far fewer than items: start at ≤ 2M slots
     # (32 MiB of keys + counts) and grow on overflow (bounded probe runs)
-    full = min(_pow2(2 * max(nw, 1)), _TABLE_MAX)
-    cap = min(full, INITIAL_TABLE)
+    full = min(_pow2(2 * max(ni, 1)), _TABLE_MAX)
+    cap = min(full, initial)
     while True:
         tkeys = torch.zeros(cap, dtype=torch.int64, device=dev)
         tcounts = torch.zeros(cap, dtype=torch.int64, device=dev)
         ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        if nw:
-            _call("hbmr_wc_insert", _ptr(buf), n, _ptr(starts), _ptr(lens), _ptr(weights), nw,
-                  _ptr(tkeys), _ptr(tcounts), cap, _ptr(ovf), _st(stream))
+        if ni:
+            _call(insert, _ptr(buf), n, _ptr(starts), _ptr(lens), _ptr(weights), ni, _ptr(tkeys),
+                  _ptr(tcounts), cap, _ptr(ovf), _st(stream))
         if int(ovf) == 0:
             break
         if cap >= full:
-            raise RuntimeError(f"word table overflow at {cap} slots for {nw} words")
+            raise RuntimeError(f"{what[0]} table overflow at {cap} slots for {ni} {what[1]}")
         cap = min(cap * 4, full)
-    ustart = torch.empty(min(cap, max(nw, 1)), dtype=torch.int32, device=dev)
+    ustart = torch.empty(min(cap, max(ni, 1)), dtype=torch.int32, device=dev)
     ulen = torch.empty_like(ustart)
     ucount = torch.empty(ustart.numel(), dtype=torch.int64, device=dev)
     upart = torch.empty(ustart.numel(), dtype=torch.int32, device=dev)
     counter = torch.zeros(1, dtype=torch.int32, device=dev)
-    if nw:
-        _call("hbmr_wc_compact", _ptr(buf), n, _ptr(tkeys), _ptr(tcounts), cap, int(R),
-              _ptr(ustart), _ptr(ulen), _ptr(ucount), _ptr(upart), _ptr(counter), _st(stream))
+    if ni:
+        _call(*compact, _ptr(tkeys), _ptr(tcounts), cap, int(R), _ptr(ustart), _ptr(ulen),
+              _ptr(ucount), _ptr(upart), _ptr(counter), _st(stream))
     nu = int(counter)
     return ustart[:nu], ulen[:nu], ucount[:nu], upart[:nu]
+
+
+def aggregate(buf, starts, lens, weights=None, R=1, stream=None):
+    """Exact per-word totals: (ustart, ulen, ucount int64, upart int32), unordered.
+    ``upart`` = (Text.hashCode() & INT_MAX) % R (Hadoop's HashPartitioner)."""
+    return _aggregate("hbmr_wc_insert", ("hbmr_wc_compact", _ptr(buf), buf.numel()),
+                      ("word", "words"), INITIAL_TABLE, buf, starts, lens, weights, R, stream)
 
 
 def pack(buf, ustart, ulen, order=None, stream=None):
@@ -135,10 +152,15 @@ def merge_tables(blob: torch.Tensor, counts: torch.Tensor, R: int = 1, stream=No
     all-to-all-v of the shuffle)."""
     if blob.device.type != "cuda":
         return merge_tables_cpu(bytes(blob.numpy()), counts, R)
-    blob = _aligned(blob)
-    starts, lens = tokenize(blob, stream)
+    return _merge(tokenize, aggregate, ("word", "words"), _aligned(blob), counts, R, stream)
+
+
+def _merge(itemize, aggregate, what, blob, counts, R, stream):
+    """merge_tables of an aligned device blob whose entries ``itemize`` finds."""
+    starts, lens = itemize(blob, stream)
     if starts.numel() != counts.numel():
-        raise ValueError(f"word table mismatch: {starts.numel()} words, {counts.numel()} counts")
+        raise ValueError(f"{what[0]} table mismatch: {starts.numel()} {what[1]}, "
+                         f"{counts.numel()} counts")
     us, ul, uc, up = aggregate(blob, starts, lens, counts.contiguous(), R, stream)
     order = torch.argsort(up, stable=True)
     out = pack(blob, us, ul, order, stream)

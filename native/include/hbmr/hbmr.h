@@ -257,7 +257,6 @@ int hbmr_recsort_cuts(const uint8_t* data, const int64_t* koff, const int64_t* k
                       const uint32_t* perm, long n, const uint8_t* sp, const int64_t* sp_off,
                       const int64_t* sp_len, int nsplit, int64_t* cuts, hipStream_t st);
 int hbmr_recsort_chunk_bytes(void);
-int hbmr_recsort_set_chunk_lanes(int lanes);
 int hbmr_recsort_gather(const uint8_t* src, const uint32_t* perm, const int64_t* foff,
                         const int64_t* flen, const int64_t* dst_off, const int64_t* chunk_base,
                         const uint32_t* chunk_entry, long n, long nchunks, uint8_t* dst,

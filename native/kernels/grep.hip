@@ -22,12 +22,14 @@
 //     after the running maximum of all earlier ends is always chosen (a root);
 //     one lane walks the chain of each root up to the next root.
 //  3. span_insert / span_compact: the two-level exact hash aggregate of
-//     text.hip over explicit (start, len) spans (a match may hold spaces and
-//     end anywhere): keys are hash tag << 32 | span index + 1.
+//     bytes/span_table.h (text.hip's) over explicit (start, len) spans (a
+//     match may hold spaces and end anywhere): keys are hash tag << 32 | span
+//     index + 1.
 //  4. lines_count / lines_write: (start, len) of the '\n'-terminated entries
-//     of a match table blob.
+//     of a match table blob, by the tokenizer pair of the same header.
 #include "common.h"
 #include "../include/hbmr/hbmr.h"
+#include "bytes/span_table.h"
 
 namespace {
 
@@ -40,32 +42,6 @@ constexpr int kWaves = kThreads / HBMR_WAVE;
 constexpr int kMaxTable = 16384;             // uint16 entries: 32 KiB of LDS
 constexpr int kMaxGrid = 2048;
 constexpr uint16_t kAccept = 0x8000;         // bit 15 of an entry: the target state accepts
-
-__device__ __forceinline__ uint32_t block_reduce_add(uint32_t v, uint32_t* s_w) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) s_w[w] = v;
-  __syncthreads();
-  uint32_t t = 0;
-  for (int i = 0; i < kWaves; ++i) t += s_w[i];
-  return t;
-}
-
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t x, uint32_t* s_w) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t v = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) s_w[w] = v;
-  __syncthreads();
-  uint32_t base = 0;
-  for (int i = 0; i < w; ++i) base += s_w[i];
-  return base + v - x;
-}
 
 // 16 bytes at buf[i0..] into dst (16-byte aligned LDS); bytes at or past n read as '\n'.
 // Returns the OR of the bytes read.
@@ -287,126 +263,38 @@ __global__ __launch_bounds__(kThreads) void grep_select_write_kernel(
 }
 
 // ---------------------------------------------------------------- span aggregate
-__device__ __forceinline__ uint64_t span_hash64(const uint8_t* p, uint32_t len) {
-  uint64_t h = 1469598103934665603ull;  // FNV-1a
-  for (uint32_t i = 0; i < len; ++i) h = (h ^ p[i]) * 1099511628211ull;
-  h ^= h >> 33;                          // murmur3 fmix64
-  h *= 0xff51afd7ed558ccdull;
-  h ^= h >> 33;
-  h *= 0xc4ceb9fe1a85ec53ull;
-  h ^= h >> 33;
-  return h;
-}
-
-// the span at p (len) equals span `rep`?
-__device__ __forceinline__ bool same_span(const uint8_t* __restrict__ buf,
-                                          const uint32_t* __restrict__ starts,
-                                          const uint32_t* __restrict__ lens, uint32_t rep,
-                                          const uint8_t* p, uint32_t len) {
-  if (lens[rep] != len) return false;
-  const uint8_t* q = buf + starts[rep];
-  for (uint32_t i = 0; i < len; ++i)
-    if (q[i] != p[i]) return false;
-  return true;
-}
-
-__device__ __forceinline__ bool span_global_insert(
-    const uint8_t* __restrict__ buf, const uint32_t* __restrict__ starts,
-    const uint32_t* __restrict__ lens, uint64_t h, unsigned long long key, const uint8_t* p,
-    uint32_t len, unsigned long long wt, unsigned long long* __restrict__ tkeys,
-    unsigned long long* __restrict__ tcounts, unsigned long long mask) {
-  unsigned long long slot = h & mask;
-  // a probe run this long means the table is too full: report overflow and let
-  // the host retry with a larger table instead of crawling
-  const unsigned long long max_probe = mask < 4096ull ? mask : 4096ull;
-  for (unsigned long long probe = 0; probe <= max_probe; ++probe) {
-    unsigned long long cur = tkeys[slot];
-    if (cur == 0ull) {
-      cur = atomicCAS(&tkeys[slot], 0ull, key);
-      if (cur == 0ull) {
-        atomicAdd(&tcounts[slot], wt);
-        return true;
-      }
-    }
-    if ((cur >> 32) == (key >> 32) &&
-        same_span(buf, starts, lens, (uint32_t)(cur & 0xffffffffull) - 1u, p, len)) {
-      atomicAdd(&tcounts[slot], wt);
-      return true;
-    }
-    slot = (slot + 1) & mask;
+// a span is named by its index into starts / lens
+struct SpanRep {
+  const uint8_t* buf;
+  const uint32_t* starts;
+  const uint32_t* lens;
+  __device__ __forceinline__ uint32_t item(long w, const uint8_t*& p, uint32_t& len) const {
+    len = lens[w];
+    p = buf + starts[w];
+    return (uint32_t)w;
   }
-  return false;
-}
+  __device__ __forceinline__ bool equals(uint32_t rep, const uint8_t* p, uint32_t len) const {
+    if (lens[rep] != len) return false;
+    const uint8_t* q = buf + starts[rep];
+    for (uint32_t i = 0; i < len; ++i)
+      if (q[i] != p[i]) return false;
+    return true;
+  }
+  template <class F>
+  __device__ __forceinline__ long rep(uint32_t id, uint32_t& s, F each) const {
+    s = starts[id];
+    const uint32_t len = lens[id];
+    for (uint32_t e = 0; e < len; ++e) each(buf[s + e]);
+    return (long)s + len;
+  }
+};
 
-constexpr int kInsPerThread = 16;
-constexpr int kInsSpans = kThreads * kInsPerThread;  // spans per workgroup
-constexpr int kLdsSlots = 2048;                      // 32 KiB of LDS
-constexpr int kLdsProbes = 32;
-
-// Two-level aggregation as wc_insert: a workgroup folds its 4096 spans into an
-// LDS table (a hot match collapses there instead of hammering one global
-// counter), then inserts each distinct span once into the global table with
-// its local count.  Spans that find no LDS slot within kLdsProbes go straight
-// to the global table.
-__global__ __launch_bounds__(kThreads) void span_insert_kernel(
+__global__ __launch_bounds__(kInsThreads) void span_insert_kernel(
     const uint8_t* __restrict__ buf, const uint32_t* __restrict__ starts,
     const uint32_t* __restrict__ lens, const int64_t* __restrict__ weights, long nspans,
     unsigned long long* __restrict__ tkeys, unsigned long long* __restrict__ tcounts,
     unsigned long long mask, int* __restrict__ overflow) {
-  __shared__ unsigned long long s_keys[kLdsSlots];
-  __shared__ unsigned long long s_cnt[kLdsSlots];
-  for (int i = threadIdx.x; i < kLdsSlots; i += kThreads) {
-    s_keys[i] = 0ull;
-    s_cnt[i] = 0ull;
-  }
-  __syncthreads();
-  const long w0 = (long)blockIdx.x * kInsSpans;
-  bool ovf = false;
-#pragma unroll 1
-  for (int j = 0; j < kInsPerThread; ++j) {
-    const long w = w0 + (long)j * kThreads + threadIdx.x;
-    if (w >= nspans) break;
-    const uint32_t len = lens[w];
-    const uint8_t* p = buf + starts[w];
-    const uint64_t h = span_hash64(p, len);
-    const unsigned long long key = ((h >> 32) << 32) | (unsigned long long)((uint32_t)w + 1u);
-    const unsigned long long wt = weights ? (unsigned long long)weights[w] : 1ull;
-    uint32_t slot = (uint32_t)(h >> 7) & (kLdsSlots - 1);
-    bool done = false;
-    for (int probe = 0; probe < kLdsProbes && !done; ++probe) {
-      unsigned long long cur = s_keys[slot];
-      if (cur == 0ull) {
-        cur = atomicCAS(&s_keys[slot], 0ull, key);
-        if (cur == 0ull) {
-          atomicAdd(&s_cnt[slot], wt);
-          done = true;
-          break;
-        }
-      }
-      if ((cur >> 32) == (key >> 32) &&
-          same_span(buf, starts, lens, (uint32_t)(cur & 0xffffffffull) - 1u, p, len)) {
-        atomicAdd(&s_cnt[slot], wt);
-        done = true;
-        break;
-      }
-      slot = (slot + 1) & (kLdsSlots - 1);
-    }
-    if (!done && !span_global_insert(buf, starts, lens, h, key, p, len, wt, tkeys, tcounts, mask))
-      ovf = true;
-  }
-  __syncthreads();
-  // flush: each distinct span of this workgroup once into the global table
-  for (int i = threadIdx.x; i < kLdsSlots; i += kThreads) {
-    const unsigned long long key = s_keys[i];
-    if (key == 0ull) continue;
-    const uint32_t rep = (uint32_t)(key & 0xffffffffull) - 1u;
-    const uint32_t len = lens[rep];
-    const uint8_t* p = buf + starts[rep];
-    const uint64_t h = span_hash64(p, len);
-    if (!span_global_insert(buf, starts, lens, h, key, p, len, s_cnt[i], tkeys, tcounts, mask))
-      ovf = true;
-  }
-  if (ovf) atomicExch(overflow, 1);
+  two_level_insert(SpanRep{buf, starts, lens}, weights, nspans, tkeys, tcounts, mask, overflow);
 }
 
 __global__ __launch_bounds__(256) void span_compact_kernel(
@@ -415,75 +303,54 @@ __global__ __launch_bounds__(256) void span_compact_kernel(
     const unsigned long long* __restrict__ tcounts, long cap, int R,
     uint32_t* __restrict__ ustart, uint32_t* __restrict__ ulen, int64_t* __restrict__ ucount,
     int32_t* __restrict__ upart, unsigned int* __restrict__ counter) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= cap) return;
-  const unsigned long long k = tkeys[i];
-  if (k == 0ull) return;
-  const uint32_t rep = (uint32_t)(k & 0xffffffffull) - 1u;
-  const uint32_t s = starts[rep], len = lens[rep];
-  uint32_t jh = 1u;   // WritableComparator.hashBytes
-  for (uint32_t e = 0; e < len; ++e) jh = 31u * jh + (uint32_t)(int32_t)(int8_t)buf[s + e];
-  const unsigned int o = atomicAdd(counter, 1u);
-  ustart[o] = s;
-  ulen[o] = len;
-  ucount[o] = (int64_t)tcounts[i];
-  upart[o] = (int32_t)(((int32_t)jh & 0x7fffffff) % R);
+  table_compact(SpanRep{buf, starts, lens}, tkeys, tcounts, cap, R, ustart, ulen, ucount, upart,
+                counter);
 }
 
 // ---------------------------------------------------------------- newline spans
 // entry-start bit mask of this lane's 16 bytes: byte 0, or a byte after '\n'
-__device__ __forceinline__ uint32_t line_start_mask(const uint8_t* __restrict__ buf, long n,
-                                                    long i0) {
-  uint8_t b[kBytes];
-  if (i0 + kBytes <= n) {
-    const uint4 v = *reinterpret_cast<const uint4*>(buf + i0);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+// (the load is written out here: through text.hip's load16 both lines kernels
+// compile differently and grep.lines measured 2 % slower)
+struct LineStarts {
+  __device__ __forceinline__ uint32_t operator()(const uint8_t* __restrict__ buf, long n,
+                                                 long i0) const {
+    uint8_t b[kTokBytes];
+    if (i0 + kTokBytes <= n) {
+      const uint4 v = *reinterpret_cast<const uint4*>(buf + i0);
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-    for (int j = 0; j < kBytes; ++j) b[j] = (uint8_t)(w[j >> 2] >> ((j & 3) * 8));
-  } else {
+      for (int j = 0; j < kTokBytes; ++j) b[j] = (uint8_t)(w[j >> 2] >> ((j & 3) * 8));
+    } else {
 #pragma unroll
-    for (int j = 0; j < kBytes; ++j) b[j] = (i0 + j < n) ? buf[i0 + j] : (uint8_t)'\n';
+      for (int j = 0; j < kTokBytes; ++j) b[j] = (i0 + j < n) ? buf[i0 + j] : (uint8_t)'\n';
+    }
+    bool prev_nl = i0 == 0 ? true : buf[i0 - 1] == '\n';
+    uint32_t m = 0;
+#pragma unroll
+    for (int j = 0; j < kTokBytes; ++j) {
+      if (prev_nl && i0 + j < n) m |= 1u << j;
+      prev_nl = b[j] == '\n';
+    }
+    return m;
   }
-  bool prev_nl = i0 == 0 ? true : buf[i0 - 1] == '\n';
-  uint32_t m = 0;
-#pragma unroll
-  for (int j = 0; j < kBytes; ++j) {
-    if (prev_nl && i0 + j < n) m |= 1u << j;
-    prev_nl = b[j] == '\n';
-  }
-  return m;
-}
+};
 
-__global__ __launch_bounds__(kThreads) void lines_count_kernel(
+struct LineEnd {
+  static constexpr long kSkip = 0;   // an entry may be empty
+  __device__ __forceinline__ bool operator()(uint8_t c) const { return c == '\n'; }
+};
+
+__global__ __launch_bounds__(kTokThreads) void lines_count_kernel(
     const uint8_t* __restrict__ buf, long n, uint32_t* __restrict__ tile_counts) {
-  __shared__ uint32_t s_w[kWaves];
-  const long i0 = (long)blockIdx.x * kTile + (long)threadIdx.x * kBytes;
-  const uint32_t c = i0 < n ? (uint32_t)__popc(line_start_mask(buf, n, i0)) : 0u;
-  const uint32_t t = block_reduce_add(c, s_w);
-  if (threadIdx.x == 0) tile_counts[blockIdx.x] = t;
+  tokenize_count(buf, n, tile_counts, LineStarts{});
 }
 
-__global__ __launch_bounds__(kThreads) void lines_write_kernel(
+__global__ __launch_bounds__(kTokThreads) void lines_write_kernel(
     const uint8_t* __restrict__ buf, long n, const long* __restrict__ tile_base,
     uint32_t* __restrict__ starts, uint32_t* __restrict__ lens) {
-  __shared__ uint32_t s_w[kWaves];
-  const long i0 = (long)blockIdx.x * kTile + (long)threadIdx.x * kBytes;
-  uint32_t m = i0 < n ? line_start_mask(buf, n, i0) : 0u;
-  const uint32_t off = block_excl_scan((uint32_t)__popc(m), s_w);
-  long o = tile_base[blockIdx.x] + off;
-  while (m) {
-    const int j = __ffs(m) - 1;
-    m &= m - 1;
-    const long s = i0 + j;
-    long e = s;
-    while (e < n && buf[e] != '\n') ++e;
-    starts[o] = (uint32_t)s;
-    lens[o] = (uint32_t)(e - s);
-    ++o;
-  }
+  tokenize_write(buf, n, tile_base, starts, lens, LineStarts{}, LineEnd{});
 }
 
-inline int grid_for(long n, int per) { return (int)((n + per - 1) / per); }
 inline long tiles_of(long n) { return (n + kTile - 1) / kTile; }
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) != 0; }
 
@@ -570,7 +437,7 @@ int hbmr_span_insert(const uint8_t* buf, long n, const uint32_t* starts, const u
   if (nspans == 0) return 0;
   if (cap <= 0 || (cap & (cap - 1)) != 0 || n >= 0xffffffffl || nspans >= 0xffffffffl)
     return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(span_insert_kernel, dim3(grid_for(nspans, kInsSpans)), dim3(kThreads), 0,
+  hipLaunchKernelGGL(span_insert_kernel, dim3(grid_for(nspans, kInsItems)), dim3(kThreads), 0,
                      stream, buf, starts, lens, weights, nspans,
                      reinterpret_cast<unsigned long long*>(tkeys),
                      reinterpret_cast<unsigned long long*>(tcounts),

@@ -31,6 +31,7 @@
 //     the keys: 0.45 vs 0.97 ms and 1.06 vs 1.33 ms, same profile).
 #include "common.h"
 #include "../include/hbmr/hbmr.h"
+#include "bytes/records.h"
 
 namespace {
 
@@ -38,8 +39,6 @@ constexpr int kThreads = 256;
 constexpr int kLanes = 16;                    // lanes per key pair, per tuple, per copy chunk
 constexpr int kStep = kLanes * 16;            // bytes a lane group covers in one step
 int g_two_level = 1;                          // hbmr_recjoin_set_two_level (A/B)
-
-inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 
 // per source the addresses of data, foff, flen, koff, klen (a device table: the
 // source of a tuple varies per thread)
@@ -106,30 +105,6 @@ __global__ __launch_bounds__(kThreads) void recjoin_heads_kernel(
   }
 }
 
-__device__ __forceinline__ uint64_t round_key0(const uint8_t* p, long len) {
-  const int nb = len < 7 ? (int)len : 7;
-  uint64_t k = 0;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) k = (k << 8) | (j < nb ? (uint64_t)p[j] : 0);
-  return (k << 8) | (uint64_t)(len < 8 ? len : 8);
-}
-
-// compareBytes(a, b) given that the first `from` bytes are equal, 8 bytes a step
-__device__ __forceinline__ int compare_from(const uint8_t* a, long la, const uint8_t* b, long lb,
-                                            long from) {
-  const long n = la < lb ? la : lb;
-  long i = from;
-  for (; i + 8 <= n; i += 8) {
-    uint64_t x, y;
-    __builtin_memcpy(&x, a + i, 8);
-    __builtin_memcpy(&y, b + i, 8);
-    if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;
-  }
-  for (; i < n; ++i)
-    if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-
 struct Heads {             // the group heads of one source
   const uint8_t* data;
   const int64_t* koff;
@@ -149,7 +124,7 @@ __global__ __launch_bounds__(kThreads) void recjoin_rank_kernel(
   long lo = 0, hi = t.n, from = 0;
   bool full = true;                            // a full compare decides inside [lo, hi)
   if (two_level) {
-    const uint64_t rk = round_key0(q, ql);
+    const uint64_t rk = round_key(q, ql);
     long a = 0, b = t.n;                       // first head whose round key is >= rk
     while (a < b) {
       const long mid = (a + b) >> 1;
@@ -301,20 +276,8 @@ __global__ __launch_bounds__(kThreads) void recjoin_copy_kernel(
   const long p = chunk_entry[g];
   const long c = g - chunk_base[p];
   const long a = pdst[p];
-  const long end = a + plen[p];
-  const long mis = (long)(reinterpret_cast<uintptr_t>(dst + a) & 15);
-  const long slot = a - mis + c * kStep + lane * 16L;
-  long b = slot > a ? slot : a;
-  const long e = slot + 16 < end ? slot + 16 : end;
-  if (b >= e) return;
-  const uint8_t* q = reinterpret_cast<const uint8_t*>((uintptr_t)psrc[p]) + (b - a);
-  if (e - b == 16) {
-    uint4 v;
-    __builtin_memcpy(&v, q, 16);               // the source has whatever alignment it has
-    *reinterpret_cast<uint4*>(dst + b) = v;
-  } else {
-    for (; b < e; ++b, ++q) dst[b] = *q;
-  }
+  copy_slot(dst, a, a + plen[p], c, lane,
+            [&] { return reinterpret_cast<const uint8_t*>((uintptr_t)psrc[p]); });
 }
 
 }  // namespace

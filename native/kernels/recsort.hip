@@ -40,9 +40,11 @@
 //     while the lanes of a wave are not idle on a 300-byte record.  A chunk
 //     finds its record in a chunk → entry table (one load; a binary search
 //     over the chunk offsets per chunk cost as much as the copy itself:
-//     tools/bench_recsort.py, profiles/sort_1gpu.json).
+//     profiles/sort_1gpu.json).  The slot copy is bytes/records.h's, shared
+//     with recjoin.hip's piece copy.
 #include "common.h"
 #include "../include/hbmr/hbmr.h"
+#include "bytes/records.h"
 
 #include <algorithm>
 
@@ -50,10 +52,8 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kKeyLanes = 16;                 // lanes per key in the hash kernel
-int g_chunk_lanes = 16;                       // lanes per gather chunk (hbmr_recsort_set_chunk_lanes, A/B)
 constexpr uint64_t kContinues = 8;            // low byte of a round key: more bytes follow
 
-inline long ceil_div(long a, long b) { return (a + b - 1) / b; }
 inline long align_up(long a, long b) { return ceil_div(a, b) * b; }
 
 __host__ __device__ constexpr uint32_t pow31(uint32_t e) {
@@ -100,11 +100,7 @@ __global__ __launch_bounds__(kThreads) void recsort_round_keys_kernel(
   long left = klen[r] - 7L * d;
   if (left < 0) left = 0;
   const uint8_t* p = data + koff[r] + 7L * d;
-  const int nb = left < 7 ? (int)left : 7;
-  uint64_t k = 0;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) k = (k << 8) | (j < nb ? (uint64_t)p[j] : 0);
-  keys[i] = (k << 8) | (uint64_t)(left < 8 ? left : 8);
+  keys[i] = round_key(p, left);
   vals[i] = (uint32_t)i;
 }
 
@@ -229,14 +225,6 @@ __global__ __launch_bounds__(kThreads) void recsort_apply_kernel(
   }
 }
 
-__device__ __forceinline__ int compare_bytes(const uint8_t* a, long la, const uint8_t* b,
-                                             long lb) {
-  const long n = la < lb ? la : lb;
-  for (long i = 0; i < n; ++i)
-    if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
-
 __global__ void recsort_cuts_kernel(const uint8_t* __restrict__ data,
                                     const int64_t* __restrict__ koff,
                                     const int64_t* __restrict__ klen,
@@ -253,53 +241,27 @@ __global__ void recsort_cuts_kernel(const uint8_t* __restrict__ data,
   while (lo < hi) {
     const long mid = (lo + hi) >> 1;
     const uint32_t r = perm[mid];
-    if (compare_bytes(data + koff[r], klen[r], q, ql) < 0) lo = mid + 1;
+    if (compare_from(data + koff[r], klen[r], q, ql, 0) < 0) lo = mid + 1;
     else hi = mid;
   }
   cuts[s] = lo;
 }
 
-// kLanes consecutive lanes copy one chunk of kLanes 16-byte slots
-template <int kLanes>
+// kCopyLanes consecutive lanes copy one chunk of a frame
 __global__ __launch_bounds__(kThreads) void recsort_gather_kernel(
     const uint8_t* __restrict__ src, const uint32_t* __restrict__ perm,
     const int64_t* __restrict__ foff, const int64_t* __restrict__ flen,
     const int64_t* __restrict__ dst_off, const int64_t* __restrict__ chunk_base,
     const uint32_t* __restrict__ chunk_entry, long n, long nchunks, uint8_t* __restrict__ dst) {
-  constexpr int kChunk = kLanes * 16;
-  const long g = (long)blockIdx.x * (kThreads / kLanes) + (threadIdx.x / kLanes);
+  const long g = (long)blockIdx.x * (kThreads / kCopyLanes) + (threadIdx.x / kCopyLanes);
   if (g >= nchunks) return;
-  const int lane = threadIdx.x % kLanes;
-  long lo = 0;                       // the entry of chunk g: chunk_base[lo] <= g < chunk_base[lo + 1]
-  if (chunk_entry != nullptr) {
-    lo = chunk_entry[g];
-  } else {
-    long hi = n;                     // chunk_base[n] = nchunks
-    while (hi - lo > 1) {
-      const long mid = (lo + hi) >> 1;
-      if (chunk_base[mid] <= g) lo = mid;
-      else hi = mid;
-    }
-  }
+  const int lane = threadIdx.x % kCopyLanes;
+  const long lo = chunk_entry[g];    // chunk g's entry: chunk_base[lo] <= g < chunk_base[lo + 1]
   const long c = g - chunk_base[lo];
   const long rec = perm ? (long)perm[lo] : lo;
   const long len = flen[rec];
-  // offsets into dst: the frame is [a, end); this lane's slot is 16-byte aligned in memory
-  const long a = dst_off[lo];
-  const long end = a + len;
-  const long mis = (long)(reinterpret_cast<uintptr_t>(dst + a) & 15);
-  const long slot = a - mis + c * kChunk + lane * 16L;
-  long b = slot > a ? slot : a;
-  const long e = slot + 16 < end ? slot + 16 : end;
-  if (b >= e) return;
-  const uint8_t* q = src + foff[rec] + (b - a);
-  if (e - b == 16) {
-    uint4 v;
-    __builtin_memcpy(&v, q, 16);      // the source has whatever alignment it has
-    *reinterpret_cast<uint4*>(dst + b) = v;
-  } else {
-    for (; b < e; ++b, ++q) dst[b] = *q;
-  }
+  const long a = dst_off[lo];        // offset into dst: the frame is [a, a + len)
+  copy_slot(dst, a, a + len, c, lane, [&] { return src + foff[rec]; });
 }
 
 }  // namespace
@@ -389,33 +351,21 @@ int hbmr_recsort_cuts(const uint8_t* data, const int64_t* koff, const int64_t* k
   return (int)hipGetLastError();
 }
 
-int hbmr_recsort_chunk_bytes(void) { return g_chunk_lanes * 16; }
-
-// lanes that share a gather chunk: 16, 32 or 64 (A/B; read by the caller through
-// hbmr_recsort_chunk_bytes when it counts chunks)
-int hbmr_recsort_set_chunk_lanes(int lanes) {
-  if (lanes != 16 && lanes != 32 && lanes != 64) return (int)hipErrorInvalidValue;
-  g_chunk_lanes = lanes;
-  return 0;
-}
+int hbmr_recsort_chunk_bytes(void) { return kCopyChunk; }
 
 // dst[dst_off[i] : + flen[r]] = src[foff[r] : + flen[r]] with r = perm[i] (perm
 // null: r = i), i < n.  chunk_base[n + 1]: the exclusive scan of each entry's
 // chunk count ((dst address & 15) + flen[r] + chunk - 1) / chunk, chunk =
-// hbmr_recsort_chunk_bytes() at the time of this call.  chunk_entry[nchunks]: the
-// entry each chunk belongs to (null: a binary search over chunk_base per chunk).
+// hbmr_recsort_chunk_bytes().  chunk_entry[nchunks]: the entry each chunk belongs to.
 int hbmr_recsort_gather(const uint8_t* src, const uint32_t* perm, const int64_t* foff,
                         const int64_t* flen, const int64_t* dst_off, const int64_t* chunk_base,
                         const uint32_t* chunk_entry, long n, long nchunks, uint8_t* dst,
                         hipStream_t st) {
   if (n <= 0 || nchunks <= 0) return 0;
-  const int lanes = g_chunk_lanes;
-  const long grid = ceil_div(nchunks, kThreads / lanes);
-  if (grid >= (1L << 31)) return (int)hipErrorInvalidValue;
-  auto kernel = lanes == 16 ? recsort_gather_kernel<16>
-                            : (lanes == 32 ? recsort_gather_kernel<32> : recsort_gather_kernel<64>);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kThreads), 0, st, src, perm, foff, flen,
-                     dst_off, chunk_base, chunk_entry, n, nchunks, dst);
+  const long grid = ceil_div(nchunks, kThreads / kCopyLanes);
+  if (grid >= (1L << 31) || chunk_entry == nullptr) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(recsort_gather_kernel, dim3((unsigned)grid), dim3(kThreads), 0, st, src, perm,
+                     foff, flen, dst_off, chunk_base, chunk_entry, n, nchunks, dst);
   return (int)hipGetLastError();
 }
 

@@ -33,9 +33,6 @@ from hbmr.ops import recsort  # noqa: E402
 from hbmr.ops import sort as tsort  # noqa: E402
 
 
-DEFAULT_LANES = recsort.chunk_lanes()
-
-
 def _put_be32(buf, offs, vals):
     for j in range(4):
         buf[offs + j] = ((vals >> (24 - 8 * j)) & 0xFF).astype(np.uint8)
@@ -106,22 +103,12 @@ def map_pipeline(data, index, nparts, reps):
     sort = timed(lambda: recsort.sort_perm(data, index, nparts), reps)
     lens = index[1][perm.long()]
     dst = torch.cumsum(lens, 0) - lens
-    by_lanes = {}
-    for lanes in (16, 32, 64, DEFAULT_LANES):       # back to back; ends on the default
-        recsort.set_chunk_lanes(lanes)
-        by_lanes[lanes] = timed(lambda: recsort.gather_frames(data, perm, index[0], index[1], dst,
-                                                              blob.numel(), check=False), reps)
-    gath = by_lanes[DEFAULT_LANES]
-    recsort.CHUNK_MAP = False
-    search = timed(lambda: recsort.gather_frames(data, perm, index[0], index[1], dst, blob.numel(),
-                                                 check=False), reps)
-    recsort.CHUNK_MAP = True
+    gath = timed(lambda: recsort.gather_frames(data, perm, index[0], index[1], dst, blob.numel(),
+                                               check=False), reps)
     return {"records": n, "bytes": nb, "partitions": nparts, "rounds": stats["rounds"],
             "pipeline_ms": round(total * 1e3, 2), "pipeline_gb_per_s": round(nb / total / 1e9, 2),
             "partition_ms": round(part * 1e3, 3), "rounds_ms": round((sort - part) * 1e3, 2),
             "gather_ms": round(gath * 1e3, 3),
-            "gather_ms_by_chunk_lanes": {str(k): round(v * 1e3, 3) for k, v in by_lanes.items()},
-            "gather_ms_chunk_search": round(search * 1e3, 3),
             "gather_gb_per_s_copied": round(blob.numel() / gath / 1e9, 1),
             "gather_gb_per_s_read_plus_written": round(2 * blob.numel() / gath / 1e9, 1)}
 
