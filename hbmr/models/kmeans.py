@@ -20,6 +20,12 @@ DistributedCache):
                          no-op.  Reducer r commits clusters of partition r to
                          the job output directory (if one is set).
 
+Host structure of a GPU map batch: ``_MapBatch`` (tasks by combiner path, the
+output slabs, the baselines' installation) is shared by the bf16 arm
+(``_map_gpu_batch``) and the exact arm (``_map_exact``), which keep only their
+op calls.  ``reduce`` is the collective and the output; the new centroids come
+from ``_reduce_device`` or ``_reduce_host``.
+
 Inputs: ``synthetic:<points>:<seed>`` (a Gaussian mixture generated directly
 into HBM by a counter-based generator, identical on CPU and GPU) or a path of
 SequenceFiles of (LongWritable, FloatVectorWritable).
@@ -267,9 +273,33 @@ def _sum_slabs(outs):
     return sums, counts
 
 
-_EXACT_STATS: dict = {}
-_EXACT_SKIPPED: dict = {}
+# Exact mode's device counters of one iteration, per (kind, cin, device): an
+# int64 tensor with one entry per reported counter of the kind.
+_EXACT_COUNTERS = {"stats": ("EXACT_FLAGGED_POINTS", "EXACT_RELABELLED_POINTS",
+                             "EXACT_NEIGHBOUR_SCANS"),
+                   "skipped": ("EXACT_BOUND_SKIPPED_POINTS",)}
+_EXACT_DEVICE: dict = {}
 _EXACT_LOCK = threading.Lock()
+
+
+def _exact_counter(kind, cin, device):
+    """Device counters ``kind`` of exact mode for one iteration ("stats":
+    flagged, relabelled, neighbour scans; "skipped": the points the bounded
+    assign skipped), created zeroed on first use."""
+    key = (kind, cin, str(device))
+    with _EXACT_LOCK:
+        t = _EXACT_DEVICE.get(key)
+        if t is None:
+            t = _EXACT_DEVICE[key] = torch.zeros(len(_EXACT_COUNTERS[kind]), dtype=torch.int64,
+                                                 device=device)
+        return t
+
+
+def _pop_exact_counters(cin, device):
+    """[(counter names, device tensor)] of the iteration, taken out of the table."""
+    got = ((names, _EXACT_DEVICE.pop((kind, cin, str(device)), None))
+           for kind, names in _EXACT_COUNTERS.items())
+    return [(names, t) for names, t in got if t is not None]
 
 # Reference partitions of the delta combiner, per (split, device, k, dp,
 # fx_shift, exact) in this (worker) process; least recently used first.  A
@@ -280,34 +310,77 @@ _BASE_LOCK = threading.Lock()
 _BASE_MAX = 4096
 
 
-def _baseline_plan(ctxs, datas, k, dp, fx, exact, enabled):
-    """Split a batch into tasks with a usable baseline (delta path), tasks that
-    get one from this batch (direct combiner, then installed) and the rest
-    (direct combiner only: a second attempt of a split in the same batch)."""
-    have, new, plain = [], [], []
-    bases, keys = [], []
-    seen = set()
-    dev = str(ctxs[0].device)
-    with _BASE_LOCK:
-        for i, (c, d) in enumerate(zip(ctxs, datas)):
-            sp = c.spec.split
-            sk = sp.get("key") if enabled and isinstance(sp, dict) else None
-            key = None if sk is None else (sk, dev, k, dp, fx, exact)
-            keys.append(key)
-            if key is None or key in seen:
-                plain.append(i)
-                bases.append(None)
-                continue
-            seen.add(key)
-            b = _BASELINES.get(key)
-            x = d.xb if exact else d
-            if b is not None and b.data_ptr == x.data_ptr() and b.n == x.shape[0]:
-                have.append(i)
-                bases.append(b)
-            else:
-                new.append(i)
-                bases.append(None)
-    return have, new, plain, bases, keys
+class _MapBatch:
+    """One map batch on one stream: its tasks by combiner path and its output
+    slabs.  Tasks with a usable baseline (``have``: delta path), tasks that
+    get one from this batch (``new``: direct combiner, then installed) and the
+    rest (``plain``: direct combiner only — a second attempt of a split in the
+    same batch, or no delta combiner).  The [B, k, dp] / [B, k] slabs hold the
+    tasks in ``have + new + plain`` order, so each path writes one contiguous
+    run; ``out[i]`` is task i's (sums, counts) view of them, whatever its path."""
+
+    def __init__(self, ctxs, datas, k, img, exact, enabled):
+        self.ctxs, self.datas, self.exact = ctxs, datas, exact
+        self.have, self.new, self.plain = [], [], []
+        self.bases, self.keys = [], []
+        self.installed = []         # (key, Baseline) this batch updated or created
+        seen = set()
+        dev = str(ctxs[0].device)
+        with _BASE_LOCK:
+            for i, (c, d) in enumerate(zip(ctxs, datas)):
+                sp = c.spec.split
+                sk = sp.get("key") if enabled and isinstance(sp, dict) else None
+                key = None if sk is None else (sk, dev, k, img.dp, img.fx_shift, exact)
+                self.keys.append(key)
+                if key is None or key in seen:
+                    self.plain.append(i)
+                    continue
+                seen.add(key)
+                b = _BASELINES.get(key)
+                x = self._rows(i)
+                if b is not None and b.data_ptr == x.data_ptr() and b.n == x.shape[0]:
+                    self.have.append(i)
+                    self.bases.append(b)
+                else:
+                    self.new.append(i)
+        B = len(datas)
+        self.sums = torch.empty(B, k, img.dp, dtype=torch.int64, device=ctxs[0].device)
+        self.counts = torch.empty(B, k, dtype=torch.int64, device=ctxs[0].device)
+        self.out = [None] * B
+        for i, s, c in zip(self.have + self.new + self.plain, self.sums.unbind(0),
+                           self.counts.unbind(0)):
+            self.out[i] = (s, c)
+
+    def _rows(self, i):
+        return self.datas[i].xb if self.exact else self.datas[i]
+
+    def delta_slabs(self):
+        """The slabs of the ``have`` tasks, for the delta path's one call."""
+        H = len(self.have)
+        return self.sums[:H], self.counts[:H]
+
+    def advanced(self):
+        """The delta path ran: the baselines' partials are this batch's slabs."""
+        for i, b in zip(self.have, self.bases):
+            b.S0, b.N0 = self.out[i]
+            self.installed.append((self.keys[i], b))
+
+    def install(self, i, g):
+        """Labels ``g`` of ``new`` task i become its split's reference partition."""
+        from ..ops import kmeans as km
+        x = self._rows(i)
+        self.installed.append((self.keys[i], km.Baseline(g, *self.out[i], x.data_ptr(),
+                                                         x.shape[0])))
+
+    def finish(self, grown=None):
+        """Install the baselines, count the records; the per-task views in task order."""
+        ctx = self.ctxs[0]
+        if self.installed:
+            _install_baselines(self.installed, ctx.stream, getattr(ctx, "split_cache", None),
+                               grown)
+        for c, d in zip(self.ctxs, self.datas):
+            c.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, d.shape[0])
+        return self.out
 
 
 def _baseline_bytes(b) -> int:
@@ -356,26 +429,6 @@ def _install_baselines(entries, stream, cache=None, grown=None):
                 with _BASE_LOCK:
                     if _BASELINES.get(key) is b:
                         _BASELINES.pop(key)
-
-
-def _exact_stats(cin, device):
-    """Device counters (flagged, relabelled) of exact mode for one iteration."""
-    key = (cin, str(device))
-    with _EXACT_LOCK:
-        t = _EXACT_STATS.get(key)
-        if t is None:
-            t = _EXACT_STATS[key] = torch.zeros(3, dtype=torch.int64, device=device)
-        return t
-
-
-def _exact_skipped(cin, device):
-    """Device counter of the points the bounded assign skipped in one iteration."""
-    key = (cin, str(device))
-    with _EXACT_LOCK:
-        t = _EXACT_SKIPPED.get(key)
-        if t is None:
-            t = _EXACT_SKIPPED[key] = torch.zeros(1, dtype=torch.int64, device=device)
-        return t
 
 
 class KMeansSplitJob(SplitJob):
@@ -467,11 +520,9 @@ class KMeansSplitJob(SplitJob):
         if spec.kind == "synthetic":
             p = spec.params
             return synthetic_points(p["seed"], p["start"], p["n"], self.d, self.centers, device)
-        return self._load_file_split(spec.params, device)
-
-    def _load_fp32(self, spec: SplitSpec, device):
-        # bf16 is the storage precision of the points on every slot type
-        return self._load_raw(spec, device).to(torch.bfloat16)
+        dev = torch.device(device)
+        host = self._read_points(spec.params, dev.type == "cuda")
+        return self._to_device(host, dev) if dev.type == "cuda" else host
 
     def split_nbytes(self, data) -> int:
         nb = getattr(data, "nbytes", None)
@@ -479,63 +530,57 @@ class KMeansSplitJob(SplitJob):
             return int(nb())
         return super().split_nbytes(data)
 
-    def load_split_host(self, spec: SplitSpec):
-        """Host half of a file split's load (native decode into pinned memory),
-        run by the GPU runtime's loader threads in parallel; None for synthetic
-        splits (they are generated on the device)."""
-        if spec.kind != "file":
-            return None
+    def _read_points(self, p, pinned: bool):
+        """A SequenceFile split → fp32 [n, d] on the host: the native reader
+        decodes the records straight into (pinned) memory in one pass, sized
+        for the most records the byte range can hold (a record is >=
+        4+4+8+4+4d bytes)."""
         from ..io import nativeio
-        p = spec.params
-        # one pass: size for the most records the byte range can hold (a record
-        # is >= 4+4+8+4+4d bytes), decode straight into pinned memory
         n = p["length"] // (20 + 4 * self.d) + 2
-        host = torch.empty(n, self.d, dtype=torch.float32,
-                           pin_memory=torch.cuda.is_available())
+        host = torch.empty(n, self.d, dtype=torch.float32, pin_memory=pinned)
         got = nativeio.read_points_into(p["path"], p["start"], p["length"], host.data_ptr(),
                                         self.d, n)
         return host[:got]
 
-    def load_split_from_host(self, spec: SplitSpec, host, device):
-        """Device half: one async H2D on the current stream, bf16 + padding."""
-        from ..ops import kmeans as km
+    @staticmethod
+    def _to_device(host, device):
+        """One asynchronous H2D copy on the current (slot) stream.  The pinned
+        buffer must outlive the copy: it is kept until the stream has passed."""
         x = host.to(device, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         _PINNED_INFLIGHT.append((ev, host))
         while _PINNED_INFLIGHT and _PINNED_INFLIGHT[0][0].query():
             _PINNED_INFLIGHT.pop(0)
-        if self.exact:
-            return km.ExactSplit(x, km.padded_dim(self.d), self.exact_dtype)
-        xb = x.to(torch.bfloat16)
+        return x
+
+    def _resident(self, x, device):
+        """fp32 rows on a GPU → the split as its maps read it: an ExactSplit
+        (exact mode keeps the fp32 data beside the 16-bit copy), else bf16 —
+        the storage precision of the points on every slot type — zero-padded
+        to dp columns."""
+        from ..ops import kmeans as km
         dp = km.padded_dim(self.d)
+        if self.exact:
+            return km.ExactSplit(x, dp, self.exact_dtype)
+        xb = x.to(torch.bfloat16)
         if dp == self.d:
             return xb.contiguous()
         out = torch.zeros(xb.shape[0], dp, dtype=torch.bfloat16, device=device)
         out[:, :self.d] = xb
         return out
 
-    def _load_file_split(self, p, device):
-        """A SequenceFile split → fp32 [n, d] on ``device``: the native reader
-        decodes the records straight into pinned host memory, then one
-        asynchronous H2D copy on the current (slot) stream."""
-        from ..io import nativeio
-        n = p["length"] // (20 + 4 * self.d) + 2
-        dev = torch.device(device)
-        host = torch.empty(n, self.d, dtype=torch.float32, pin_memory=dev.type == "cuda")
-        got = nativeio.read_points_into(p["path"], p["start"], p["length"], host.data_ptr(),
-                                        self.d, n)
-        host = host[:got]
-        if dev.type != "cuda":
-            return host
-        x = host.to(dev, non_blocking=True)
-        # the pinned buffer must outlive the copy: keep it until the stream passes
-        ev = torch.cuda.Event()
-        ev.record()
-        _PINNED_INFLIGHT.append((ev, host))
-        while _PINNED_INFLIGHT and _PINNED_INFLIGHT[0][0].query():
-            _PINNED_INFLIGHT.pop(0)
-        return x
+    def load_split_host(self, spec: SplitSpec):
+        """Host half of a file split's load (native decode into pinned memory),
+        run by the GPU runtime's loader threads in parallel; None for synthetic
+        splits (they are generated on the device)."""
+        if spec.kind != "file":
+            return None
+        return self._read_points(spec.params, torch.cuda.is_available())
+
+    def load_split_from_host(self, spec: SplitSpec, host, device):
+        """Device half: one async H2D on the current stream, bf16 + padding."""
+        return self._resident(self._to_device(host, device), device)
 
     def load_split_sample(self, spec: SplitSpec, device, fraction: float):
         if spec.kind == "synthetic":
@@ -547,41 +592,30 @@ class KMeansSplitJob(SplitJob):
         return super().load_split_sample(spec, device, fraction)
 
     def load_split(self, spec: SplitSpec, device):
-        from ..ops import kmeans as km
-        if self.exact:
-            # exact mode keeps the fp32 data: CPU slots compute on it directly,
-            # GPU slots hold it beside the bf16 copy
-            x = self._load_raw(spec, device)
-            if str(device) == "cpu":
-                return x.contiguous()
-            return km.ExactSplit(x, km.padded_dim(self.d), self.exact_dtype)
-        xb = self._load_fp32(spec, device)
+        x = self._load_raw(spec, device)
         if str(device) == "cpu":
-            return xb.to(torch.float32)
-        dp = km.padded_dim(self.d)
-        if dp == self.d:
-            return xb.contiguous()
-        out = torch.zeros(xb.shape[0], dp, dtype=torch.bfloat16, device=device)
-        out[:, :self.d] = xb
-        return out
+            # CPU slots compute on fp32: exact mode's data as it is, else the
+            # bf16 roundings every slot type stores
+            return x.contiguous() if self.exact else x.to(torch.bfloat16).to(torch.float32)
+        return self._resident(x, device)
 
     # -- map ------------------------------------------------------------------------
     @staticmethod
-    def _scratch(ctx, ns, k):
-        """Per-(tracker, stream) label + combiner workspace, reused across tasks
-        (tasks on one stream are ordered, so reuse is race-free)."""
-        from ..ops import kmeans as km
-        key = ("kmeans-scratch", str(ctx.device), id(ctx.stream))
+    def _stream_scratch(ctx, kind) -> dict:
+        """Per-(tracker, stream) scratch buffers (ops.kmeans.scratch_buf), reused
+        across tasks (tasks on one stream are ordered, so reuse is race-free)."""
         store = ctx.tracker.__dict__.setdefault("_scratch", {})
-        ws, labels = store.get(key, (None, None))
+        return store.setdefault((kind, str(ctx.device), id(ctx.stream)), {})
+
+    @classmethod
+    def _scratch(cls, ctx, ns, k):
+        """The bf16 arm's combiner workspace and labels for splits of sizes ``ns``."""
+        from ..ops import kmeans as km
+        scratch = cls._stream_scratch(ctx, "kmeans-scratch")
         need_lab, need_ws = km.batch_scratch_sizes(ns, k)
         need_ws = max(need_ws, km.delta_workspace_bytes(int(sum(ns)), len(ns), k))
-        if ws is None or ws.numel() < need_ws:
-            ws = torch.empty(max(need_ws, 1 << 20), dtype=torch.uint8, device=ctx.device)
-        if labels is None or labels.numel() < need_lab:
-            labels = torch.empty(max(need_lab, 1), dtype=torch.int32, device=ctx.device)
-        store[key] = (ws, labels)
-        return ws, labels
+        return (km.scratch_buf(scratch, "ws", need_ws, torch.uint8, ctx.device, floor=1 << 20),
+                km.scratch_buf(scratch, "labels", need_lab, torch.int32, ctx.device, floor=1))
 
     def map_gpu(self, ctx, points):
         return self.map_gpu_batch([ctx], [points])[0]
@@ -609,52 +643,32 @@ class KMeansSplitJob(SplitJob):
             torch.cuda.current_stream().wait_event(ready)
         for t in (img.cbf, img.chalf):
             t.record_stream(torch.cuda.current_stream())
-        B = len(datas)
+        delta = self.combiner == "delta"
         if self.exact:
-            return self._map_exact(ctxs, datas, img)
-        have, new, plain, bases, keys = _baseline_plan(
-            ctxs, datas, self.k, img.dp, img.fx_shift, False, self.combiner == "delta")
+            return self._map_exact(ctxs, datas, img, delta)
         ws, labels = self._scratch(ctx, [d.shape[0] for d in datas], self.k)
-        sums = torch.empty(B, self.k, img.dp, dtype=torch.int64, device=ctx.device)
-        counts = torch.empty(B, self.k, dtype=torch.int64, device=ctx.device)
-        order = have + new + plain
-        H = len(have)
-        S, N = sums.unbind(0), counts.unbind(0)     # slab views in task order `order`
-        out = [None] * B
-        for j, i in enumerate(order):
-            out[i] = (S[j], N[j])
-        installed = []
-        if have:
-            hb = [bases[i] for i in have]
-            km.map_batch_delta([datas[i] for i in have], img, sums[:H], counts[:H], labels, ws,
-                               hb, stream=ctx.stream)
-            for i, b in zip(have, hb):
-                b.S0, b.N0 = out[i]
-                installed.append((keys[i], b))
-        rest = new + plain
+        mb = _MapBatch(ctxs, datas, self.k, img, False, delta)
+        if mb.have:
+            km.map_batch_delta([datas[i] for i in mb.have], img, *mb.delta_slabs(), labels, ws,
+                               mb.bases, stream=ctx.stream)
+            mb.advanced()
+        rest = mb.new + mb.plain
         if rest:
-            km.map_batch_gpu([datas[i] for i in rest], img, sums[H:], counts[H:], labels, ws,
+            H = len(mb.have)
+            km.map_batch_gpu([datas[i] for i in rest], img, mb.sums[H:], mb.counts[H:], labels, ws,
                              stream=ctx.stream, zero_outputs=True)
-            if new:
+            if mb.new:
                 # this batch's labels become the new splits' reference partitions
-                # (one allocation for all of them)
-                total = sum(datas[i].shape[0] for i in rest)
-                gall = labels[:total].clone()
+                # (one allocation for all of them; the new ones come first)
+                gall = labels[:sum(datas[i].shape[0] for i in rest)].clone()
                 off = 0
-                newset = set(new)
-                for i in rest:
+                for i in mb.new:
                     n = datas[i].shape[0]
-                    if keys[i] is not None and i in newset:
-                        installed.append((keys[i], km.Baseline(gall[off:off + n], *out[i],
-                                                                datas[i].data_ptr(), n)))
+                    mb.install(i, gall[off:off + n])
                     off += n
-        if installed:
-            _install_baselines(installed, ctx.stream, getattr(ctx, "split_cache", None))
-        for c, d in zip(ctxs, datas):
-            c.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, d.shape[0])
-        return out
+        return mb.finish()
 
-    def _map_exact(self, ctxs, datas, img):
+    def _map_exact(self, ctxs, datas, img, delta):
         """Exact mode: per task top-3 assign and certification / fp64 re-score,
         then ONE fp32-row combiner call for the batch (delta against the
         splits' reference partitions where they exist).  The flagged /
@@ -665,70 +679,41 @@ class KMeansSplitJob(SplitJob):
         if TRACE.on:
             TRACE.instant("kmeans.map_exact", n=len(datas))
         ctx = ctxs[0]
-        store = ctx.tracker.__dict__.setdefault("_scratch", {})
-        scratch = store.setdefault(("kmeans-exact", str(ctx.device), id(ctx.stream)), {})
-        stats = _exact_stats(self.cin, ctx.device)
-        have, new, plain, bases, keys = _baseline_plan(
-            ctxs, datas, self.k, img.dp, img.fx_shift, True, self.combiner == "delta")
-        B = len(datas)
-        sums = torch.empty(B, self.k, img.dp, dtype=torch.int64, device=ctx.device)
-        counts = torch.empty(B, self.k, dtype=torch.int64, device=ctx.device)
-        order = have + new + plain
-        pos = {i: j for j, i in enumerate(order)}
-        H = len(have)
-        installed = []
+        scratch = self._stream_scratch(ctx, "kmeans-exact")
+        stats = _exact_counter("stats", self.cin, ctx.device)
+        mb = _MapBatch(ctxs, datas, self.k, img, True, delta)
         grown = None
-        if have:
-            ns = [datas[i].shape[0] for i in have]
-            total = sum(ns)
-            lab = scratch.get("labcat")
-            if lab is None or lab.numel() < total:
-                lab = scratch["labcat"] = torch.empty(total, dtype=torch.int32, device=ctx.device)
-            need = km.delta_workspace_bytes(total, H, self.k)
-            if scratch.get("dws") is None or scratch["dws"].numel() < need:
-                scratch["dws"] = torch.empty(need, dtype=torch.uint8, device=ctx.device)
-            hb = [bases[i] for i in have]
-            bounded = self.bounds and self.combiner == "delta" and km.bounds_supported(img)
+        if mb.have:
+            xs = [datas[i] for i in mb.have]
+            total = sum(x.shape[0] for x in xs)
+            lab = km.scratch_buf(scratch, "labcat", total, torch.int32, ctx.device)
+            dws = km.scratch_buf(scratch, "dws", km.delta_workspace_bytes(total, len(xs), self.k),
+                                 torch.uint8, ctx.device)
+            bounds = skipped = None
+            bounded = self.bounds and delta and km.bounds_supported(img)
             if bounded:
                 # points whose stored bound outlasts the centroids' shift keep
                 # their label unassigned; the bounds ride on the baselines and
                 # hold for the labels ``g`` only: every exact job over the
                 # split shares the baseline whatever its conf, so a job that
                 # advances ``g`` without them (below) drops them
-                nogap = [b for b in hb if b.gap is None]
-                km.assign_exact_batch([datas[i] for i in have], img, stats, lab, scratch,
-                                      stream=ctx.stream, bounds=hb,
-                                      skipped=_exact_skipped(self.cin, ctx.device))
+                nogap = [b for b in mb.bases if b.gap is None]
+                bounds, skipped = mb.bases, _exact_counter("skipped", self.cin, ctx.device)
+            km.assign_exact_batch(xs, img, stats, lab, scratch, stream=ctx.stream, bounds=bounds,
+                                  skipped=skipped)
+            if bounded:
                 grown = {id(b): b.gap.numel() * b.gap.element_size() for b in nogap}
-            else:
-                km.assign_exact_batch([datas[i] for i in have], img, stats, lab, scratch,
-                                      stream=ctx.stream)
-            km.delta_combine([datas[i].x32 for i in have], lab, self.k, sums[:H], counts[:H],
-                             scratch["dws"], hb, fx_shift=img.fx_shift, stream=ctx.stream,
-                             keep_bounds=bounded)
-            for i, b in zip(have, hb):
-                b.S0, b.N0 = sums[pos[i]], counts[pos[i]]
-                installed.append((keys[i], b))
-        for i in new + plain:
-            d = datas[i]
-            s, c = sums[pos[i]], counts[pos[i]]
+            km.delta_combine([x.x32 for x in xs], lab, self.k, *mb.delta_slabs(), dws, mb.bases,
+                             fx_shift=img.fx_shift, stream=ctx.stream, keep_bounds=bounded)
+            mb.advanced()
+        for i in mb.new + mb.plain:
+            s, c = mb.out[i]
             s.zero_()
             c.zero_()
-            lab = km.assign_exact(d, img, stats, scratch, stream=ctx.stream)
-            need = km.workspace_bytes(d.shape[0], img.k)
-            if scratch.get("ws") is None or scratch["ws"].numel() < need:
-                scratch["ws"] = torch.empty(max(need, 1 << 20), dtype=torch.uint8,
-                                            device=ctx.device)
-            km.accumulate(d.x32, lab, img.k, s, c, fx_shift=img.fx_shift, stream=ctx.stream,
-                          workspace=scratch["ws"])
-            if keys[i] is not None and i in new:
-                b = km.Baseline(lab.clone(), s, c, d.xb.data_ptr(), d.shape[0])
-                installed.append((keys[i], b))
-        if installed:
-            _install_baselines(installed, ctx.stream, getattr(ctx, "split_cache", None), grown)
-        for c, d in zip(ctxs, datas):
-            c.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, d.shape[0])
-        return [(sums[pos[i]], counts[pos[i]]) for i in range(B)]
+            lab = km.map_split_exact(datas[i], img, s, c, scratch, stats, stream=ctx.stream)
+            if i in mb.new:
+                mb.install(i, lab.clone())
+        return mb.finish(grown)
 
     def map_cpu(self, ctx, points):
         from ..ops import kmeans as km
@@ -783,7 +768,10 @@ class KMeansSplitJob(SplitJob):
         return sums, counts
 
     def reduce(self, ctx, combined):
-        from ..ops import kmeans as km
+        """The collective, then the new centroids on the device (_reduce_device)
+        or the host (_reduce_host: CPU trackers, simulated GPUs) — each returns
+        (shift, points, host centroids for rank 0's output or None) — then the
+        job output, the saved centroid version and the result."""
         from ..utils.trace import TRACE
         sums, counts = combined
         k, dp = sums.shape
@@ -798,119 +786,111 @@ class KMeansSplitJob(SplitJob):
                 ctx.sim_ready = max(time.time(), getattr(ctx, "sim_base", 0.0)) + sim
         sums = packed[:k * dp].view(k, dp)
         counts = packed[k * dp:]
+        device = sums.device.type == "cuda"
         # exact mode's device counters are read with the shift, after the
         # update is enqueued and the staged maps released (a host read here
         # would wait for every map kernel and leave the device idle until the
         # update and the next job's maps were launched)
-        est = _EXACT_STATS.pop((self.cin, str(sums.device)), None) \
-            if self.exact and sums.device.type == "cuda" else None
-        esk = _EXACT_SKIPPED.pop((self.cin, str(sums.device)), None) \
-            if self.exact and sums.device.type == "cuda" else None
+        counters = _pop_exact_counters(self.cin, sums.device) if self.exact and device else []
         killed = getattr(ctx, "killed", None)
         if killed is not None and killed():
             raise RuntimeError("reduce killed (collective restart): result not published")
-        if sums.device.type == "cuda":
-            old = STORE.image(self.cin, sums.device)
-            # the previous job's reduce built it on a stream of its own
-            # (splitexec._reduce_stream): order the read behind it even where
-            # no local map output (which waited on that job's gate) orders it
-            ready = getattr(old, "ready", None)
-            if ready is not None:
-                torch.cuda.current_stream().wait_event(ready)
-            img = km.CentroidImage.__new__(km.CentroidImage)
-            img.__dict__.update(old.__dict__)
-            img.cen = old.cen.clone()
-            img.cbf = old.cbf.clone()
-            img.chalf = old.chalf.clone()
-            img.shift2 = torch.zeros_like(old.shift2)
-            img.refresh(sums, counts)
-            if self.exact:
-                # the 16-bit operand image and the centroid neighbour table
-                # (one native kernel each) the next job's first kernels read:
-                # built here, behind the update, so the gate's event covers them
-                img.image16(self.exact_dtype)
-                img.neighbors()
-            img.ready = torch.cuda.Event()
-            img.ready.record()
-            # the host copy of the new centroids (rank 0's saved version, the
-            # returned centroids) is enqueued now, right behind the update: on
-            # the tracker's shared reduce stream a later read-back would queue
-            # behind the next job's combine, which waits for that job's maps —
-            # this job then finished a whole iteration late
-            host_cen = cen_ev = None
-            if ctx.rank == 0 and (self.cdir or self.conf.get_boolean(RETURN_KEY, False)):
-                host_cen = torch.empty(tuple(img.cen.shape), dtype=torch.float32,
-                                       pin_memory=True)
-                host_cen.copy_(img.cen, non_blocking=True)
-                cen_ev = torch.cuda.Event()
-                cen_ev.record()
-            if TRACE.on:
-                TRACE.instant("kmeans.refresh_launched")
-            STORE.put_image(self.cout, sums.device, img)
-            # the next iteration's staged maps may go on the device now, behind
-            # the update kernel (hbmr/gpu/gates.py); the host sync comes after
-            rel = getattr(ctx, "release_dependents", None)
-            if rel is not None:
-                rel()
-            # the shift, the point count (and exact mode's counters) in one
-            # device->host copy (one sync)
-            vals = [img.shift2.max().double().sqrt(), counts.sum().double()]
-            if est is not None:
-                vals += list(est.double().unbind(0))
-            if esk is not None:
-                vals.append(esk[0].double())
-            got = torch.stack(vals).tolist()
-            shift, npts = got[0], got[1]
-            if esk is not None:
-                ctx.reporter.incrCounter("KMEANS", "EXACT_BOUND_SKIPPED_POINTS", int(got[-1]))
-            if est is not None:
-                for name, v in zip(("EXACT_FLAGGED_POINTS", "EXACT_RELABELLED_POINTS",
-                                    "EXACT_NEIGHBOUR_SCANS"), got[2:5]):
-                    ctx.reporter.incrCounter("KMEANS", name, int(v))
-            if TRACE.on:
-                TRACE.instant("kmeans.shift_synced")
-            new_cen = None
+        if device:
+            shift, npts, cen = self._reduce_device(ctx, sums, counts, counters)
         else:
-            host_cen = cen_ev = None
-            old = STORE.host_centroids(self.cin)
-            if sim is not None:
-                # no-data rehearsal: every partial is zero, the centroids stay
-                # (the device's update kernel is part of the modelled time)
-                new_cen, shift, npts = old, 0.0, 0
-            else:
-                cnt = counts.to(torch.float64)[:, None]
-                s = sums[:, :self.d].to(torch.float64) / float(1 << self.fx_shift)
-                new_cen = torch.where(cnt > 0, s / cnt.clamp(min=1),
-                                      old.to(torch.float64)).to(torch.float32)
-                shift = float((new_cen - old).norm(dim=1).max()) if self.k else 0.0
-                npts = int(counts.sum().item())
-            STORE.put_host(self.cout, new_cen)
-            rel = getattr(ctx, "release_dependents", None)
-            if rel is not None:
-                rel()
-            if sim is not None:
-                # the real reduce's host sync on the shift: done when the
-                # (simulated) device result is
-                delay = ctx.sim_ready - time.time()
-                if delay > 0:
-                    time.sleep(delay)
-        self._write_output(ctx, counts, new_cen)
+            shift, npts, cen = self._reduce_host(ctx, sums, counts, sim)
+        self._write_output(ctx, counts)
         if TRACE.on:
             TRACE.instant("kmeans.output_written")
         res = {"shift": shift, "points": int(npts), "centroids_key": self.cout}
-        if host_cen is not None:
-            cen_ev.synchronize()
         if ctx.rank == 0 and self.cdir:
-            cen = new_cen if new_cen is not None else host_cen
             _save_centroids(self.cdir, self.cout, cen[:, :self.d])
         if ctx.rank == 0 and self.conf.get_boolean(RETURN_KEY, False):
             # the new centroids travel back with the result (the client may live
             # in another process than the reduce, e.g. with GPU worker processes)
-            cen = new_cen if new_cen is not None else host_cen
             res["centroids"] = encode_centroids(cen[:, :self.d])
         if TRACE.on:
             TRACE.instant("kmeans.reduce_return")
         return res
+
+    @staticmethod
+    def _release_dependents(ctx):
+        """The next iteration's staged maps may go on the device now, behind
+        the update (hbmr/gpu/gates.py); a reduce's host sync comes after."""
+        rel = getattr(ctx, "release_dependents", None)
+        if rel is not None:
+            rel()
+
+    def _reduce_device(self, ctx, sums, counts, counters):
+        from ..utils.trace import TRACE
+        old = STORE.image(self.cin, sums.device)
+        # the previous job's reduce built it on a stream of its own
+        # (splitexec._reduce_stream): order the read behind it even where
+        # no local map output (which waited on that job's gate) orders it
+        ready = getattr(old, "ready", None)
+        if ready is not None:
+            torch.cuda.current_stream().wait_event(ready)
+        img = old.successor(sums, counts)
+        if self.exact:
+            # the 16-bit operand image and the centroid neighbour table
+            # (one native kernel each) the next job's first kernels read:
+            # built here, behind the update, so the gate's event covers them
+            img.image16(self.exact_dtype)
+            img.neighbors()
+        img.ready = torch.cuda.Event()
+        img.ready.record()
+        # the host copy of the new centroids (rank 0's saved version, the
+        # returned centroids) is enqueued now, right behind the update: on
+        # the tracker's shared reduce stream a later read-back would queue
+        # behind the next job's combine, which waits for that job's maps —
+        # this job then finished a whole iteration late
+        host_cen = None
+        if ctx.rank == 0 and (self.cdir or self.conf.get_boolean(RETURN_KEY, False)):
+            host_cen = torch.empty(tuple(img.cen.shape), dtype=torch.float32, pin_memory=True)
+            host_cen.copy_(img.cen, non_blocking=True)
+            cen_ev = torch.cuda.Event()
+            cen_ev.record()
+        if TRACE.on:
+            TRACE.instant("kmeans.refresh_launched")
+        STORE.put_image(self.cout, sums.device, img)
+        self._release_dependents(ctx)
+        # the shift, the point count (and exact mode's counters) in one
+        # device->host copy (one sync)
+        vals = [img.shift2.max().double().sqrt(), counts.sum().double()]
+        for _, t in counters:
+            vals += list(t.double().unbind(0))
+        got = torch.stack(vals).tolist()
+        names = [name for ns, _ in counters for name in ns]
+        for name, v in zip(names, got[2:]):
+            ctx.reporter.incrCounter("KMEANS", name, int(v))
+        if TRACE.on:
+            TRACE.instant("kmeans.shift_synced")
+        if host_cen is not None:
+            cen_ev.synchronize()
+        return got[0], got[1], host_cen
+
+    def _reduce_host(self, ctx, sums, counts, sim):
+        old = STORE.host_centroids(self.cin)
+        if sim is not None:
+            # no-data rehearsal: every partial is zero, the centroids stay
+            # (the device's update kernel is part of the modelled time)
+            new_cen, shift, npts = old, 0.0, 0
+        else:
+            cnt = counts.to(torch.float64)[:, None]
+            s = sums[:, :self.d].to(torch.float64) / float(1 << self.fx_shift)
+            new_cen = torch.where(cnt > 0, s / cnt.clamp(min=1),
+                                  old.to(torch.float64)).to(torch.float32)
+            shift = float((new_cen - old).norm(dim=1).max()) if self.k else 0.0
+            npts = int(counts.sum().item())
+        STORE.put_host(self.cout, new_cen)
+        self._release_dependents(ctx)
+        if sim is not None:
+            # the real reduce's host sync on the shift: done when the
+            # (simulated) device result is
+            delay = ctx.sim_ready - time.time()
+            if delay > 0:
+                time.sleep(delay)
+        return shift, npts, new_cen
 
     def poison_result(self, ctx):
         """Fault injection (hbmr.faultinject.reduce.fail.after.release.attempt):
@@ -925,7 +905,7 @@ class KMeansSplitJob(SplitJob):
                     STORE.images.pop(key)
                     STORE.host[self.cout] = img.cen.detach().to("cpu")[:, :self.d] + 1.0
 
-    def _write_output(self, ctx, counts, new_cen):
+    def _write_output(self, ctx, counts):
         out = self.conf.get("mapred.output.dir")
         if not out:
             return
@@ -933,7 +913,7 @@ class KMeansSplitJob(SplitJob):
 
         from ..io import sequencefile as seqf
         from ..io.writable import FloatVectorWritable, IntWritable
-        cen = new_cen if new_cen is not None else STORE.host_centroids(self.cout)
+        cen = STORE.host_centroids(self.cout)     # a host reduce just put them there
         W = ctx.world_size
         per = math.ceil(self.k / W)
         lo, hi = ctx.rank * per, min(self.k, (ctx.rank + 1) * per)

@@ -11,9 +11,16 @@ Data layout contract (built by :class:`hbmr.gpu.split_cache.SplitCache`):
   int64 counts ``[k]`` — exact and order-independent, so K-Means results are
   bitwise reproducible for any placement of map tasks over CPUs/GPUs and any
   GPU count (integer RCCL all-reduce is exact too).
+
+Host plumbing every arm shares: ``_on`` (stream context), ``scratch_buf``
+(buffers grown on demand, also used by hbmr.models.kmeans), ``_check_rows`` /
+``_check_stats`` (argument checks) and ``order_after`` (the cross-stream rule
+of the reference partitions).  Exact mode's batch is ``_RefineBatch``: the
+per-call constants and the ctypes tables over a group's splits, built once.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -21,14 +28,10 @@ import threading
 import torch
 
 from . import _lib
+from ._lib import ptr
 from ..utils.trace import TRACE
 
 SUPPORTED_DP = (64, 128, 256)
-
-
-def _nullctx():
-    import contextlib
-    return contextlib.nullcontext()
 FX_SHIFT = 24  # fixed-point fraction bits of the partial sums
 # exact mode's Elkan scan: neighbours listed per centroid (past them the scan
 # checks every centroid); HBMR_KMEANS_NBR_L overrides
@@ -46,8 +49,39 @@ def padded_k(k: int) -> int:
     return ((k + 63) // 64) * 64
 
 
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
+def _on(stream):
+    """``torch.cuda.stream(stream)``; nothing for None (the caller's current stream)."""
+    return contextlib.nullcontext() if stream is None else torch.cuda.stream(stream)
+
+
+def scratch_buf(scratch: dict, key, n: int, dtype, device, floor: int = 0) -> torch.Tensor:
+    """``scratch[key]``: a flat buffer of at least ``n`` elements, kept across
+    calls and replaced (by one of ``max(n, floor)``) only when it is too small.
+    It may be longer than asked for: the kernels take pointers and counts."""
+    buf = scratch.get(key)
+    if buf is None or buf.numel() < n:
+        buf = scratch[key] = torch.empty(max(n, floor), dtype=dtype, device=device)
+    return buf
+
+
+def _top3_scratch(scratch: dict, kind: str, n: int, device):
+    """The top-3 assign's (cand [2n], scores [n], margin [2n]) of ``kind``."""
+    return (scratch_buf(scratch, (kind, "cand"), 2 * n, torch.int32, device)[:2 * n],
+            scratch_buf(scratch, (kind, "scores"), n, torch.float32, device)[:n],
+            scratch_buf(scratch, (kind, "margin"), 2 * n, torch.float32, device)[:2 * n])
+
+
+def _check_rows(xs, dp: int, dtypes=None) -> None:
+    """Every x: contiguous ``[n, dp]`` rows, all of one dtype (among ``dtypes``)."""
+    dt = xs[0].dtype
+    if (dtypes is not None and dt not in dtypes) or \
+            any(x.dtype != dt or x.shape[1] != dp or not x.is_contiguous() for x in xs):
+        raise ValueError(f"splits must be contiguous [n, {dp}] rows of one type ({dtypes})")
+
+
+def _check_stats(stats: torch.Tensor) -> None:
+    if stats.dtype != torch.int64 or stats.numel() < 3:
+        raise ValueError("stats must be int64 [3]")
 
 
 def new_partials(k: int, dp: int, device) -> tuple[torch.Tensor, torch.Tensor]:
@@ -61,6 +95,73 @@ def partials_to_float(sums: torch.Tensor, counts: torch.Tensor, d: int | None = 
     if d is not None:
         s = s[:, :d]
     return s, counts.to(torch.float64)
+
+
+def _build_image16(img: "CentroidImage", dtype):
+    """(c16, chalf, |c|, max |c|, |c - c~|, max, tiled c16 or None) of ``img``
+    on the current stream (hbmr_kmeans_image16, hbmr_kmeans_image16_tiled)."""
+    dev = img.cen.device
+    c16 = torch.empty(img.k_pad, img.dp, dtype=dtype, device=dev)
+    ch = torch.empty(img.k_pad, dtype=torch.float32, device=dev)
+    cn = torch.empty(img.k, dtype=torch.float32, device=dev)
+    ce = torch.empty(img.k, dtype=torch.float32, device=dev)
+    mx = torch.empty(2, dtype=torch.float32, device=dev)
+    rc = _lib.load().hbmr_kmeans_image16(
+        ptr(img.cen), img.k, img.d, img.dp, img.k_pad, int(dtype == torch.float16), ptr(c16),
+        ptr(ch), ptr(cn), ptr(ce), ptr(mx), _lib.stream_handle(None))
+    _lib.check(rc, "hbmr_kmeans_image16")
+    c16t = None
+    if img.dp in (64, 128):
+        # the v3 fused assign's tiled copy (hbmr_kmeans_image16_tiled)
+        c16t = torch.empty_like(c16)
+        rc = _lib.load().hbmr_kmeans_image16_tiled(ptr(c16), img.k_pad, img.dp, ptr(c16t),
+                                                   _lib.stream_handle(None))
+        _lib.check(rc, "hbmr_kmeans_image16_tiled")
+    return c16, ch, cn, mx[0:1], ce, mx[1:2], c16t
+
+
+def _neighbors_native(img: "CentroidImage", L: int):
+    """(indices [k, L], distances [k, L], L, pair distances or None) in one
+    kernel (hbmr_kmeans_centroid_nbr): pairwise fp64 distances, bounds rounded
+    outward, per-row bitonic sort in LDS — instead of ~40 small torch launches
+    whose host time held the interpreter lock at the iteration seam."""
+    dev = img.cen.device
+    di = torch.empty(img.k, L, dtype=torch.int32, device=dev)
+    f = torch.empty(img.k, L, dtype=torch.float32, device=dev)
+    pd = torch.empty(img.k, img.k, dtype=torch.float32, device=dev) \
+        if img.k <= PAIR_DIST_MAX_K else None
+    rc = _lib.load().hbmr_kmeans_centroid_nbr(ptr(img.cen), img.k, img.d, L, ptr(di), ptr(f),
+                                              ptr(pd), _lib.stream_handle(None))
+    _lib.check(rc, "hbmr_kmeans_centroid_nbr")
+    return di, f, L, pd
+
+
+def _neighbors_torch(img: "CentroidImage", L: int):
+    """The same table where the native kernel does not apply: squared
+    distances by the Gram form in fp64 (one DGEMM instead of a pairwise
+    kernel: ~0.8 ms per image at k = 1024), with the form's rounding error
+    bounded explicitly: |D2 - D| <= (d + 4) 2^-53 (|a|^2 + |b|^2) for fp32
+    inputs, so the lower bounds (Elkan's scan order and stop rule) and upper
+    bounds (the pair rule) stay rigorous."""
+    c = img.cen.double()
+    n2 = (c * c).sum(1)
+    nsum = n2[:, None] + n2[None, :]
+    d2 = torch.addmm(nsum, c, c.T, beta=1.0, alpha=-2.0)
+    err = nsum * ((img.d + 4) * 2.0 ** -53 * 1.01)
+    lo = (d2 - err).clamp_(min=0.0).sqrt_()
+    lo.fill_diagonal_(0.0)
+    dv, di = lo.sort(dim=1, stable=True)
+    dv, di = dv[:, :L].contiguous(), di[:, :L].to(torch.int32).contiguous()
+    f = dv.float()
+    f = torch.where(f.double() > dv, torch.nextafter(f, torch.full_like(f, -1.0)), f)
+    # the full matrix of upper bounds rounded UP (the pair rule of the
+    # certification's step 1); k <= PAIR_DIST_MAX_K
+    pd = None
+    if img.k <= PAIR_DIST_MAX_K:
+        hi = (d2 + err).clamp_(min=0.0).sqrt_()
+        hi.fill_diagonal_(0.0)
+        pd = _f32_up(hi).contiguous()
+    return di, f.contiguous(), L, pd
 
 
 class CentroidImage:
@@ -77,21 +178,49 @@ class CentroidImage:
         self.cbf = torch.zeros(self.k_pad, self.dp, dtype=torch.bfloat16, device=device)
         self.chalf = torch.empty(self.k_pad, dtype=torch.float32, device=device)
         self.shift2 = torch.zeros(self.k, dtype=torch.float32, device=device)
+        self._lock = threading.Lock()
         self.refresh()
+
+    def successor(self, sums, counts) -> "CentroidImage":
+        """The next iteration's image, on the current stream: private copies of
+        this one's buffers, updated from the reduced ``sums`` / ``counts``
+        (``refresh``).  This image stays as it is; the new one has its own
+        empty 16-bit image / neighbour caches and nothing else of this one's."""
+        img = CentroidImage.__new__(CentroidImage)
+        img.k, img.d, img.dp, img.k_pad = self.k, self.d, self.dp, self.k_pad
+        img.fx_shift, img.device = self.fx_shift, self.device
+        img.cen = self.cen.clone()
+        img.cbf = self.cbf.clone()
+        img.chalf = self.chalf.clone()
+        img.shift2 = torch.zeros_like(self.shift2)
+        img._lock = threading.Lock()
+        img.refresh(sums, counts)
+        return img
 
     def refresh(self, sums=None, counts=None, stream=None):
         """Reduce-side update: c = sums/counts (clusters with count 0 keep their
         centroid), then rebuild the bf16 image and -||c||²/2."""
         lib = _lib.load()
-        rc = lib.hbmr_kmeans_update(_ptr(sums), _ptr(counts), self.fx_shift, self.k, self.d,
-                                    self.dp, self.k_pad, _ptr(self.cen), _ptr(self.cbf),
-                                    _ptr(self.chalf), _ptr(self.shift2),
+        rc = lib.hbmr_kmeans_update(ptr(sums), ptr(counts), self.fx_shift, self.k, self.d,
+                                    self.dp, self.k_pad, ptr(self.cen), ptr(self.cbf),
+                                    ptr(self.chalf), ptr(self.shift2),
                                     _lib.stream_handle(stream))
         _lib.check(rc, "hbmr_kmeans_update")
         self._img16 = {}       # exact mode's 16-bit images and neighbour table: on demand
-        self._nbr = None
-        if getattr(self, "_nbr_lock", None) is None:
-            self._nbr_lock = threading.Lock()
+        self._nbr = {}
+
+    def _once(self, cache: dict, key, build):
+        """``cache[key]``, built once per image by ``build()`` on the first
+        caller's stream; every caller's current stream waits for that build."""
+        with self._lock:
+            ent = cache.get(key)
+            if ent is None:
+                vals = build()
+                ev = torch.cuda.Event()
+                ev.record()
+                ent = cache[key] = (ev, vals)
+        torch.cuda.current_stream().wait_event(ent[0])
+        return ent[1]
 
     def set_centroids(self, centroids: torch.Tensor, stream=None):
         self.cen.copy_(centroids.to(self.cen.device, torch.float32))
@@ -103,39 +232,13 @@ class CentroidImage:
         -|c~|²/2, |c_j| [k], max |c_j| [1], |c_j - c~_j| [k], max [1]) — norms
         and rounding errors in fp64 rounded up (hbmr_kmeans_image16), built
         once per image on the first caller's stream; other streams wait."""
-        with self._nbr_lock:
-            cache = self.__dict__.setdefault("_img16", {})
-            ent = cache.get(dtype)
-            if ent is None:
-                dev = self.cen.device
-                c16 = torch.empty(self.k_pad, self.dp, dtype=dtype, device=dev)
-                ch = torch.empty(self.k_pad, dtype=torch.float32, device=dev)
-                cn = torch.empty(self.k, dtype=torch.float32, device=dev)
-                ce = torch.empty(self.k, dtype=torch.float32, device=dev)
-                mx = torch.empty(2, dtype=torch.float32, device=dev)
-                rc = _lib.load().hbmr_kmeans_image16(
-                    _ptr(self.cen), self.k, self.d, self.dp, self.k_pad,
-                    int(dtype == torch.float16), _ptr(c16), _ptr(ch), _ptr(cn), _ptr(ce),
-                    _ptr(mx), _lib.stream_handle(None))
-                _lib.check(rc, "hbmr_kmeans_image16")
-                c16t = None
-                if self.dp in (64, 128):
-                    # the v3 fused assign's tiled copy (hbmr_kmeans_image16_tiled)
-                    c16t = torch.empty_like(c16)
-                    rc = _lib.load().hbmr_kmeans_image16_tiled(
-                        _ptr(c16), self.k_pad, self.dp, _ptr(c16t), _lib.stream_handle(None))
-                    _lib.check(rc, "hbmr_kmeans_image16_tiled")
-                ev = torch.cuda.Event()
-                ev.record()
-                ent = cache[dtype] = (c16, ch, cn, mx[0:1], ce, mx[1:2], ev, c16t)
-        torch.cuda.current_stream().wait_event(ent[6])
-        return ent[:6]
+        return self._once(self._img16, dtype, lambda: _build_image16(self, dtype))[:6]
 
     def image16_tiled(self, dtype=torch.float16):
         """The tiled copy of ``image16(dtype)[0]`` (32-row tiles, 16-byte pieces
         piece-major) the v3 fused assign stages lane-linearly, or None (dp > 128)."""
         self.image16(dtype)
-        return self._img16[dtype][7]
+        return self._img16[dtype][1][6]
 
     def norms(self, dtype=torch.float16):
         """(|c_j| [k], max_j |c_j| [1], |c_j - c~_j| [k], max_j |c_j - c~_j| [1])
@@ -147,69 +250,18 @@ class CentroidImage:
         """Each centroid's L nearest centroids (itself first) and their
         distances, fp64 rounded DOWN to fp32 — exact mode's Elkan scan.  Built
         once per image on the first caller's stream; other streams wait on it."""
-        with self._nbr_lock:
-            if self._nbr is None:
-                if L is None:
-                    L = int(os.environ.get("HBMR_KMEANS_NBR_L", NBR_L))
-                L = max(1, min(L, self.k))
-                if self.cen.is_cuda and self.k <= NBR_NATIVE_MAX_K and self.d <= 256:
-                    # one kernel (hbmr_kmeans_centroid_nbr): pairwise fp64
-                    # distances, bounds rounded outward, per-row bitonic sort
-                    # in LDS — instead of ~40 small torch launches whose host
-                    # time held the interpreter lock at the iteration seam
-                    dev = self.cen.device
-                    di = torch.empty(self.k, L, dtype=torch.int32, device=dev)
-                    f = torch.empty(self.k, L, dtype=torch.float32, device=dev)
-                    pd = torch.empty(self.k, self.k, dtype=torch.float32, device=dev) \
-                        if self.k <= PAIR_DIST_MAX_K else None
-                    rc = _lib.load().hbmr_kmeans_centroid_nbr(
-                        _ptr(self.cen), self.k, self.d, L, _ptr(di), _ptr(f), _ptr(pd),
-                        _lib.stream_handle(None))
-                    _lib.check(rc, "hbmr_kmeans_centroid_nbr")
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    self._nbr = (di, f, L, ev, pd)
-                    di, f, L, ev, _ = self._nbr
-                    torch.cuda.current_stream().wait_event(ev)
-                    return di, f, L
-                # squared distances by the Gram form in fp64 (one DGEMM instead
-                # of a pairwise kernel: ~0.8 ms per image at k = 1024), with
-                # the form's rounding error bounded explicitly: |D2 - D| <=
-                # (d + 4) 2^-53 (|a|^2 + |b|^2) for fp32 inputs, so the lower
-                # bounds (Elkan's scan order and stop rule) and upper bounds
-                # (the pair rule) stay rigorous
-                c = self.cen.double()
-                n2 = (c * c).sum(1)
-                nsum = n2[:, None] + n2[None, :]
-                d2 = torch.addmm(nsum, c, c.T, beta=1.0, alpha=-2.0)
-                err = nsum * ((self.d + 4) * 2.0 ** -53 * 1.01)
-                lo = (d2 - err).clamp_(min=0.0).sqrt_()
-                lo.fill_diagonal_(0.0)
-                dv, di = lo.sort(dim=1, stable=True)
-                dv, di = dv[:, :L].contiguous(), di[:, :L].to(torch.int32).contiguous()
-                f = dv.float()
-                f = torch.where(f.double() > dv, torch.nextafter(f, torch.full_like(f, -1.0)), f)
-                # the full matrix of upper bounds rounded UP (the pair rule of
-                # the certification's step 1); k <= PAIR_DIST_MAX_K
-                pd = None
-                if self.k <= PAIR_DIST_MAX_K:
-                    hi = (d2 + err).clamp_(min=0.0).sqrt_()
-                    hi.fill_diagonal_(0.0)
-                    pd = hi.float()
-                    pd = torch.where(pd.double() < hi, torch.nextafter(
-                        pd, torch.full_like(pd, float("inf"))), pd).contiguous()
-                ev = torch.cuda.Event()
-                ev.record()
-                self._nbr = (di, f.contiguous(), L, ev, pd)
-        di, f, L, ev, _ = self._nbr
-        torch.cuda.current_stream().wait_event(ev)
-        return di, f, L
+        def build():
+            n = int(os.environ.get("HBMR_KMEANS_NBR_L", NBR_L)) if L is None else L
+            n = max(1, min(n, self.k))
+            native = self.cen.is_cuda and self.k <= NBR_NATIVE_MAX_K and self.d <= 256
+            return (_neighbors_native if native else _neighbors_torch)(self, n)
+        return self._once(self._nbr, "table", build)[:3]
 
     def pair_dist(self):
         """|c_a - c_b| for every pair, fp64 rounded up to fp32 [k, k] (None past
         PAIR_DIST_MAX_K clusters): the certification's pair rule."""
         self.neighbors()
-        return self._nbr[4]
+        return self._nbr["table"][1][3]
 
     def max_shift(self) -> float:
         return float(self.shift2.max().sqrt().item()) if self.k else 0.0
@@ -224,8 +276,8 @@ def assign(points: torch.Tensor, img: CentroidImage, labels: torch.Tensor | None
     if labels is None:
         labels = torch.empty(n, dtype=torch.int32, device=points.device)
     lib = _lib.load()
-    rc = lib.hbmr_kmeans_assign_bf16(_ptr(points), n, dp, _ptr(img.cbf), _ptr(img.chalf),
-                                     img.k_pad, _ptr(labels), _ptr(scores),
+    rc = lib.hbmr_kmeans_assign_bf16(ptr(points), n, dp, ptr(img.cbf), ptr(img.chalf),
+                                     img.k_pad, ptr(labels), ptr(scores),
                                      _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_kmeans_assign_bf16")
     return labels
@@ -254,14 +306,8 @@ def accum_workspace(n: int, k: int, device) -> torch.Tensor:
 
     Reused across calls on the same device; callers that run accumulations on
     several streams concurrently must pass their own ``workspace``."""
-    lib = _lib.load()
-    need = int(lib.hbmr_kmeans_accum_workspace_bytes(n, k))
     key = torch.device(device)
-    ws = _workspaces.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=key)
-        _workspaces[key] = ws
-    return ws
+    return scratch_buf(_workspaces, key, workspace_bytes(n, k), torch.uint8, key, floor=1 << 20)
 
 
 def accumulate(points: torch.Tensor, labels: torch.Tensor, k: int, sums: torch.Tensor,
@@ -285,8 +331,8 @@ def accumulate(points: torch.Tensor, labels: torch.Tensor, k: int, sums: torch.T
     fn, name = ((lib.hbmr_kmeans_accum_f32, "hbmr_kmeans_accum_f32")
                 if points.dtype == torch.float32 else
                 (lib.hbmr_kmeans_accum_bf16, "hbmr_kmeans_accum_bf16"))
-    rc = fn(_ptr(points), n, dp, _ptr(labels), k, _ptr(sums), _ptr(counts), fx_shift,
-            _ptr(workspace), 0 if workspace is None else workspace.numel(), mode,
+    rc = fn(ptr(points), n, dp, ptr(labels), k, ptr(sums), ptr(counts), fx_shift,
+            ptr(workspace), 0 if workspace is None else workspace.numel(), mode,
             _lib.stream_handle(stream))
     _lib.check(rc, name)
 
@@ -323,8 +369,8 @@ class ExactSplit:
             self.xbn2 = torch.empty(n, dtype=torch.float32, device=dev)
             self.xerr = torch.empty(n, dtype=torch.float32, device=dev)
             rc = _lib.load().hbmr_kmeans_exact_prep(
-                _ptr(self.x32), n, dp, dp, dp, int(dtype == torch.float16), _ptr(self.xb),
-                _ptr(self.xnorm), _ptr(self.xbn2), _ptr(self.xerr), _lib.stream_handle(None))
+                ptr(self.x32), n, dp, dp, dp, int(dtype == torch.float16), ptr(self.xb),
+                ptr(self.xnorm), ptr(self.xbn2), ptr(self.xerr), _lib.stream_handle(None))
             _lib.check(rc, "hbmr_kmeans_exact_prep")
             return
         x64 = self.x32.double()
@@ -358,18 +404,28 @@ def assign_top3(points: torch.Tensor, img: CentroidImage, labels, cand, scores, 
                      (margin, torch.float32, 2)):
         if t.numel() != m * n or t.dtype != dt or not t.is_contiguous():
             raise ValueError("top-3 outputs: labels/scores [n], cand/margin [2n]")
-    f16 = points.dtype == torch.float16
-    with torch.cuda.stream(stream) if stream is not None else _nullctx():
+    with _on(stream):
         c16, ch = img.image16(points.dtype)[:2]
-    fn = "hbmr_kmeans_assign_top3_f16" if f16 else "hbmr_kmeans_assign_top3_bf16"
+    fn = "hbmr_kmeans_assign_top3_f16" if points.dtype == torch.float16 else \
+        "hbmr_kmeans_assign_top3_bf16"
     rc = getattr(_lib.load(), fn)(
-        _ptr(points), n, dp, _ptr(c16), _ptr(ch), img.k_pad, _ptr(labels),
-        _ptr(cand), _ptr(scores), _ptr(margin), _lib.stream_handle(stream))
+        ptr(points), n, dp, ptr(c16), ptr(ch), img.k_pad, ptr(labels),
+        ptr(cand), ptr(scores), ptr(margin), _lib.stream_handle(stream))
     _lib.check(rc, fn)
 
 
 REFINE_VERSION = int(os.environ.get("HBMR_REFINE", "3"))
 MAX_REFINE_BATCH = 64     # splits per refine v3 batch (the kernels' split table)
+# the pair rule of the certification keeps a [k, k] centroid distance matrix
+PAIR_DIST_MAX_K = int(os.environ.get("HBMR_PAIR_DIST_MAX_K", "8192"))
+# the native neighbour table sorts a row of k keys in LDS (k <= 8192)
+NBR_NATIVE_MAX_K = int(os.environ.get("HBMR_NBR_NATIVE_MAX_K", "8192"))
+# exact batches: one top-3 launch + one step-1 launch per up to 64 splits
+# (HBMR_EXACT_GROUPED=0: a launch of each per split)
+GROUPED_EXACT = os.environ.get("HBMR_EXACT_GROUPED", "1") != "0"
+# step 1 of the certification inside the grouped top-3 kernel's epilogue
+# (HBMR_EXACT_FUSED_Q1=0: the separate step-1 scan over materialised arrays)
+FUSED_Q1 = os.environ.get("HBMR_EXACT_FUSED_Q1", "1") != "0"
 
 
 def _check_refine_dim(img: "CentroidImage") -> None:
@@ -382,64 +438,88 @@ def _check_refine_dim(img: "CentroidImage") -> None:
         raise ValueError(f"refine v3 needs d % 8 == 0 (d = {img.d}): HBMR_REFINE=2 takes any d")
 
 
-def _refine_ws(ns: list, device, scratch: dict | None):
-    """Queue workspace of a refine v3 batch, kept in ``scratch`` across calls
-    (one stream orders the reuse)."""
-    arr = (ctypes.c_long * len(ns))(*ns)
-    need = int(_lib.load().hbmr_kmeans_refine_batch_bytes(len(ns), arr))
-    if need < 0:
-        raise ValueError("refine batch of 1..64 splits expected")
-    ws = None if scratch is None else scratch.get("refine_ws")
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.uint8, device=device)
-        if scratch is not None:
-            scratch["refine_ws"] = ws
-    return arr, ws
-
-
 class _RefineBatch:
-    """Refine v3 over a batch of splits: ``q1`` right after each split's top-3
-    assign (its candidate scratch may be reused by the next split), ``finish``
-    once (step 2 + Elkan scan over the batch's queues)."""
+    """Up to 64 splits of one exact call: its per-call constants, the ctypes
+    tables over the splits (built once, here) and refine v3 over them —
+    ``open`` before the first certification launch, ``q1`` right after each
+    split's top-3 assign (its candidate scratch may be reused by the next
+    split) or one grouped step 1 by the caller, ``finish`` once (step 2 +
+    Elkan scan over the batch's queues)."""
 
-    def __init__(self, splits: list, img: "CentroidImage", stats, scratch, stream):
+    def __init__(self, splits: list, img: "CentroidImage", stats, scratch, stream,
+                 c16=None, ch=None):
         _check_refine_dim(img)
         self.splits, self.img, self.stats, self.stream = splits, img, stats, stream
+        self.scratch = {} if scratch is None else scratch
+        self.c16, self.ch = c16, ch
         self.dt = splits[0].xb.dtype
-        self.ns, self.ws = _refine_ws([sp.shape[0] for sp in splits], splits[0].x32.device,
-                                      scratch)
-        with torch.cuda.stream(stream) if stream is not None else _nullctx():
-            self.norms = img.norms(self.dt)
-            self.nbr = img.neighbors()
-            self.pd = img.pair_dist()
-        self.labels = [None] * len(splits)
+        self.dev = splits[0].x32.device
         self.lib = _lib.load()
         self.st = _lib.stream_handle(stream)
+        self.B = B = len(splits)
+        self.sizes = [sp.shape[0] for sp in splits]
+        self.N = sum(self.sizes)
+        self.ns = (ctypes.c_long * B)(*self.sizes)
+        P = ctypes.c_void_p * B
+        self.xb, self.x32, self.xnorm, self.xbn2, self.xerr = (
+            P(*[getattr(sp, a).data_ptr() for sp in splits])
+            for a in ("xb", "x32", "xnorm", "xbn2", "xerr"))
+        self.labels = [None] * B
 
-    def q1(self, i, labels_ptr, cand, scores, margin):
+    def open(self):
+        """The queue workspace (kept in ``scratch`` across calls: one stream
+        orders the reuse) and the image's norms / neighbour table / pair
+        distances, waited for on the batch's stream."""
+        need = int(self.lib.hbmr_kmeans_refine_batch_bytes(self.B, self.ns))
+        if need < 0:
+            raise ValueError("refine batch of 1..64 splits expected")
+        self.ws = scratch_buf(self.scratch, "refine_ws", need, torch.uint8, self.dev)
+        with _on(self.stream):
+            self.norms = self.img.norms(self.dt)
+            self.nbr = self.img.neighbors()
+            self.pd = self.img.pair_dist()
+        return self
+
+    def labels_at(self, labels_ptr: int) -> None:
+        """The splits' labels lie back to back from address ``labels_ptr``."""
+        for i, n in enumerate(self.sizes):
+            self.labels[i] = labels_ptr
+            labels_ptr += 4 * n
+
+    def q1(self, i, labels_ptr: int, cand, scores, margin):
         sp, img = self.splits[i], self.img
         cn, cmax, ce, cemax = self.norms
         self.labels[i] = labels_ptr
         rc = self.lib.hbmr_kmeans_refine_batch_q1(
-            len(self.splits), self.ns, i, img.d, img.k, img.k_pad, _ptr(sp.xnorm),
-            _ptr(sp.xbn2), _ptr(sp.xerr), _ptr(cn), _ptr(cmax), _ptr(ce), _ptr(cemax),
-            labels_ptr, _ptr(cand), _ptr(scores), _ptr(margin), _ptr(self.stats),
-            _ptr(self.ws), self.ws.numel(), int(i == 0), _ptr(self.pd), self.st)
+            self.B, self.ns, i, img.d, img.k, img.k_pad, ptr(sp.xnorm),
+            ptr(sp.xbn2), ptr(sp.xerr), ptr(cn), ptr(cmax), ptr(ce), ptr(cemax),
+            labels_ptr, ptr(cand), ptr(scores), ptr(margin), ptr(self.stats),
+            ptr(self.ws), self.ws.numel(), int(i == 0), ptr(self.pd), self.st)
         _lib.check(rc, "hbmr_kmeans_refine_batch_q1")
 
     def finish(self):
-        B = len(self.splits)
         img = self.img
         _, cmax, _, cemax = self.norms
         ni, nd, L = self.nbr
-        xs = (ctypes.c_void_p * B)(*[sp.x32.data_ptr() for sp in self.splits])
-        ls = (ctypes.c_void_p * B)(*[(lp.value if isinstance(lp, ctypes.c_void_p) else lp)
-                                     for lp in self.labels])
+        ls = (ctypes.c_void_p * self.B)(*self.labels)
         rc = self.lib.hbmr_kmeans_refine_batch_finish(
-            B, self.ns, xs, ls, img.d, self.splits[0].x32.shape[1], _ptr(img.cen), img.k,
-            img.k_pad, _ptr(cmax), _ptr(cemax), _ptr(ni), _ptr(nd), L, _ptr(self.stats),
-            self.stats.numel(), _ptr(self.ws), self.ws.numel(), self.st)
+            self.B, self.ns, self.x32, ls, img.d, self.splits[0].x32.shape[1], ptr(img.cen),
+            img.k, img.k_pad, ptr(cmax), ptr(cemax), ptr(ni), ptr(nd), L, ptr(self.stats),
+            self.stats.numel(), ptr(self.ws), self.ws.numel(), self.st)
         _lib.check(rc, "hbmr_kmeans_refine_batch_finish")
+
+
+def _refine_single(lib, sp: ExactSplit, img: CentroidImage, norms, nbr, labels: int, cand: int,
+                   scores: int, margin: int, stats: torch.Tensor, st: int) -> None:
+    """The single-kernel refine (hbmr_kmeans_refine_f32) of one split;
+    ``labels`` .. ``margin`` are device addresses."""
+    cn, cmax, ce, cemax = norms
+    ni, nd, L = nbr
+    rc = lib.hbmr_kmeans_refine_f32(
+        ptr(sp.x32), sp.shape[0], img.d, sp.x32.shape[1], ptr(sp.xnorm), ptr(sp.xbn2),
+        ptr(sp.xerr), ptr(img.cen), img.k, img.k_pad, ptr(cn), ptr(cmax), ptr(ce), ptr(cemax),
+        ptr(ni), ptr(nd), L, labels, cand, scores, margin, ptr(stats), stats.numel(), st)
+    _lib.check(rc, "hbmr_kmeans_refine_f32")
 
 
 def refine_f32(split: ExactSplit, img: CentroidImage, labels, cand, scores, margin,
@@ -452,25 +532,19 @@ def refine_f32(split: ExactSplit, img: CentroidImage, labels, cand, scores, marg
     that needed the neighbour scan); a [5] stats also counts the scan's
     neighbour distances and its full scans."""
     n = split.shape[0]
-    if stats.dtype != torch.int64 or stats.numel() < 3:
-        raise ValueError("stats must be int64 [3]")
+    _check_stats(stats)
     if labels.numel() != n or cand.numel() != 2 * n or margin.numel() != 2 * n:
         raise ValueError("labels [n], cand/margin [2n] from assign_top3 expected")
     if REFINE_VERSION >= 3:
-        rb = _RefineBatch([split], img, stats, scratch, stream)
+        rb = _RefineBatch([split], img, stats, scratch, stream).open()
         rb.q1(0, labels.data_ptr(), cand, scores, margin)
         rb.finish()
         return
-    with torch.cuda.stream(stream) if stream is not None else _nullctx():
-        cn, cmax, ce, cemax = img.norms(split.xb.dtype)
-        ni, nd, L = img.neighbors()
-    rc = _lib.load().hbmr_kmeans_refine_f32(
-        _ptr(split.x32), n, img.d, split.x32.shape[1], _ptr(split.xnorm), _ptr(split.xbn2),
-        _ptr(split.xerr), _ptr(img.cen), img.k, img.k_pad, _ptr(cn), _ptr(cmax), _ptr(ce),
-        _ptr(cemax), _ptr(ni), _ptr(nd), L,
-        _ptr(labels), _ptr(cand), _ptr(scores), _ptr(margin), _ptr(stats), stats.numel(),
-        _lib.stream_handle(stream))
-    _lib.check(rc, "hbmr_kmeans_refine_f32")
+    with _on(stream):
+        norms = img.norms(split.xb.dtype)
+        nbr = img.neighbors()
+    _refine_single(_lib.load(), split, img, norms, nbr, ptr(labels), ptr(cand), ptr(scores),
+                   ptr(margin), stats, _lib.stream_handle(stream))
 
 
 def assign_exact(split: ExactSplit, img: CentroidImage, stats: torch.Tensor,
@@ -481,13 +555,14 @@ def assign_exact(split: ExactSplit, img: CentroidImage, stats: torch.Tensor,
     n = split.shape[0]
     dev = split.xb.device
     scratch = {} if scratch is None else scratch
-    key = ("exact", n)
-    bufs = scratch.get(key)
+    # one set per split size: the labels are returned, and stay a split's own
+    # until the next call over a split of the same size
+    bufs = scratch.get(("exact", n))
     if bufs is None:
-        bufs = scratch[key] = (torch.empty(n, dtype=torch.int32, device=dev),
-                               torch.empty(2 * n, dtype=torch.int32, device=dev),
-                               torch.empty(n, dtype=torch.float32, device=dev),
-                               torch.empty(2 * n, dtype=torch.float32, device=dev))
+        bufs = scratch[("exact", n)] = tuple(
+            torch.empty(m * n, dtype=t, device=dev)
+            for m, t in ((1, torch.int32), (2, torch.int32), (1, torch.float32),
+                         (2, torch.float32)))
     lab, cand, sc, mg = bufs
     assign_top3(split.xb, img, lab, cand, sc, mg, stream=stream)
     refine_f32(split, img, lab, cand, sc, mg, stats, stream=stream, scratch=scratch)
@@ -533,32 +608,20 @@ def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, ou
     total = sum(sp.shape[0] for sp in splits)
     if out.dtype != torch.int32 or out.numel() < total or not out.is_contiguous():
         raise ValueError("out must be contiguous int32 with room for every split's labels")
-    if stats.dtype != torch.int64 or stats.numel() < 3:
-        raise ValueError("stats must be int64 [3]")
+    _check_stats(stats)
     dt = splits[0].xb.dtype
-    for sp in splits:
-        if sp.xb.dtype != dt or dt not in (torch.bfloat16, torch.float16) or \
-                sp.xb.shape[1] != img.dp or not sp.xb.is_contiguous() or \
-                not sp.x32.is_contiguous():
-            raise ValueError("exact splits must hold contiguous [n, dp] rows of one 16-bit type")
-    nmax = max(sp.shape[0] for sp in splits)
+    _check_rows([sp.xb for sp in splits], img.dp, (torch.bfloat16, torch.float16))
+    if not all(sp.x32.is_contiguous() for sp in splits):
+        raise ValueError("exact splits must hold contiguous fp32 rows")
     scratch = {} if scratch is None else scratch
-    key = ("exact-batch", nmax)
-    bufs = scratch.get(key)
-    if bufs is None:
-        for kk in [kk for kk in scratch if isinstance(kk, tuple) and kk[0] == "exact-batch"]:
-            del scratch[kk]
-        bufs = scratch[key] = (torch.empty(2 * nmax, dtype=torch.int32, device=dev),
-                               torch.empty(nmax, dtype=torch.float32, device=dev),
-                               torch.empty(2 * nmax, dtype=torch.float32, device=dev))
-    cand, sc, mg = bufs
+    cand, sc, mg = _top3_scratch(scratch, "exact-batch", max(sp.shape[0] for sp in splits), dev)
     grouped = REFINE_VERSION >= 3 and img.dp <= 128 and GROUPED_EXACT
-    with torch.cuda.stream(stream) if stream is not None else _nullctx():
-        c16, ch, cn, cmax, ce, cemax = img.image16(dt)
+    with _on(stream):
+        c16, ch, *norms = img.image16(dt)
         # the neighbour table is waited for only where the certification
         # needs it (after the first top-3 launch: the reduce builds it on its
         # own stream while that assign runs)
-        ni, nd, L = (None, None, 0) if grouped else img.neighbors()
+        nbr = (None, None, 0) if grouped else img.neighbors()
         # the centroids the bounds will refer to: a private copy (the image's
         # buffers are refreshed in place), made in-stream, shared by the batch
         newref = None
@@ -569,89 +632,79 @@ def assign_exact_batch(splits: list, img: CentroidImage, stats: torch.Tensor, ou
     top3 = lib.hbmr_kmeans_assign_top3_f16 if dt == torch.float16 else \
         lib.hbmr_kmeans_assign_top3_bf16
     st = _lib.stream_handle(stream)
-    pc, ps, pm, pst = _ptr(cand), _ptr(sc), _ptr(mg), _ptr(stats)
-    pcn, pcmax, pce, pcemax, pni, pnd = (_ptr(t) for t in (cn, cmax, ce, cemax, ni, nd))
+    pc, ps, pm = ptr(cand), ptr(sc), ptr(mg)
     base, off = out.data_ptr(), 0
     for g0 in range(0, len(splits), MAX_REFINE_BATCH):
         group = splits[g0:g0 + MAX_REFINE_BATCH]
+        rb = _RefineBatch(group, img, stats, scratch, stream, c16, ch) \
+            if REFINE_VERSION >= 3 else None
         if grouped:
-            off += _exact_group(group, img, stats, base + 4 * off, c16, ch, (cn, cmax, ce, cemax),
-                                dt, scratch, stream, lib, st,
-                                None if bounds is None else bounds[g0:g0 + MAX_REFINE_BATCH],
-                                skipped, newref)
+            _exact_group(rb, base + 4 * off,
+                         None if bounds is None else bounds[g0:g0 + MAX_REFINE_BATCH],
+                         skipped, newref)
+            off += rb.N
             continue
-        rb = _RefineBatch(group, img, stats, scratch, stream) if REFINE_VERSION >= 3 else None
+        if rb is not None:
+            rb.open()
         for i, sp in enumerate(group):
             n = sp.shape[0]
-            pl = ctypes.c_void_p(base + 4 * off)
-            rc = top3(_ptr(sp.xb), n, img.dp, _ptr(c16), _ptr(ch), img.k_pad, pl, pc, ps, pm, st)
+            pl = base + 4 * off
+            rc = top3(ptr(sp.xb), n, img.dp, ptr(c16), ptr(ch), img.k_pad, pl, pc, ps, pm, st)
             _lib.check(rc, "hbmr_kmeans_assign_top3")
             if rb is not None:
                 rb.q1(i, pl, cand, sc, mg)
             else:
-                rc = lib.hbmr_kmeans_refine_f32(
-                    _ptr(sp.x32), n, img.d, sp.x32.shape[1], _ptr(sp.xnorm), _ptr(sp.xbn2),
-                    _ptr(sp.xerr), _ptr(img.cen), img.k, img.k_pad, pcn, pcmax, pce, pcemax,
-                    pni, pnd, L, pl, pc, ps, pm, pst, stats.numel(), st)
-                _lib.check(rc, "hbmr_kmeans_refine_f32")
+                _refine_single(lib, sp, img, norms, nbr, pl, pc, ps, pm, stats, st)
             off += n
         if rb is not None:
             rb.finish()
 
 
-# the pair rule of the certification keeps a [k, k] centroid distance matrix
-PAIR_DIST_MAX_K = int(os.environ.get("HBMR_PAIR_DIST_MAX_K", "8192"))
-# the native neighbour table sorts a row of k keys in LDS (k <= 8192)
-NBR_NATIVE_MAX_K = int(os.environ.get("HBMR_NBR_NATIVE_MAX_K", "8192"))
-# exact batches: one top-3 launch + one step-1 launch per up to 64 splits
-# (HBMR_EXACT_GROUPED=0: a launch of each per split)
-GROUPED_EXACT = os.environ.get("HBMR_EXACT_GROUPED", "1") != "0"
-# step 1 of the certification inside the grouped top-3 kernel's epilogue
-# (HBMR_EXACT_FUSED_Q1=0: the separate step-1 scan over materialised arrays)
-FUSED_Q1 = os.environ.get("HBMR_EXACT_FUSED_Q1", "1") != "0"
+def order_after(bases: list, attrs: tuple, st) -> None:
+    """Order a batch on stream ``st`` behind the baselines it reads.  Their
+    tensors ``attrs`` may have been written (g, gap) / allocated (S0, N0, ref)
+    on another stream — another slot's, or a reduce's: wait for the end of the
+    batch that last updated each (``event``, where its ``stream`` is not
+    ``st``), and keep the memory from being reused under this stream's pending
+    reads — once per event and per allocation: the baselines of a batch share
+    a few slabs, and an attribute that is None is skipped."""
+    events, blocks = {}, {}
+    for b in bases:
+        if b.event is not None and b.stream is not None and b.stream != st:
+            events[id(b.event)] = b.event
+        for a in attrs:
+            t = getattr(b, a)
+            if t is not None:
+                base = t._base if t._base is not None else t
+                blocks[id(base)] = base
+    for ev in events.values():
+        st.wait_event(ev)
+    for t in blocks.values():
+        t.record_stream(st)
 
 
-def _bounded_group(group, bases, img, labels_ptr, ch, norms, dt, scratch, stream, lib, st, rb,
-                   skipped, newref):
+def _bounded_group(rb: _RefineBatch, bases, labels_ptr: int, skipped, newref):
     """The bounded form of the fused grouped assign (shift, sweep, assign over
     the lists): see ``assign_exact_batch``.  ``newref``: the batch's copy of
     ``img.cen``, which the rewritten bounds refer to (``Baseline.pending``)."""
-    B = len(group)
-    ns = [sp.shape[0] for sp in group]
-    N = sum(ns)
-    dev = group[0].xb.device
-    cur = torch.cuda.current_stream() if stream is None else stream
+    img, lib = rb.img, rb.lib
+    cur = torch.cuda.current_stream() if rb.stream is None else rb.stream
     with torch.cuda.stream(cur):
-        # the reference partitions may live on another slot's stream (as in
-        # _delta_args); the centroids on a reduce's
-        events, blocks = {}, {}
-        for b in bases:
-            if b.event is not None and b.stream is not None and b.stream != cur:
-                events[id(b.event)] = b.event
-        for ev in events.values():
-            cur.wait_event(ev)
         for b in bases:
             if b.gap is None:
                 # an allocation of its own per split: it is charged to the
                 # split's cache entry and has to go when that split is evicted
-                b.gap, b.ref = torch.empty(b.g.numel(), dtype=torch.float32, device=dev), None
-        for b, n in zip(bases, ns):
+                b.gap, b.ref = torch.empty(b.g.numel(), dtype=torch.float32, device=rb.dev), None
+        for b, n in zip(bases, rb.sizes):
             if b.g.numel() != n or b.gap.numel() != n or \
                     (b.ref is not None and (tuple(b.ref.shape) != tuple(img.cen.shape) or
                                             not b.ref.is_contiguous())):
                 raise ValueError("bounds: baseline does not match its split / the centroids")
-            for t in (b.g, b.gap, b.ref):
-                if t is not None:
-                    base = t._base if t._base is not None else t
-                    blocks[id(base)] = base
-        for t in blocks.values():
-            t.record_stream(cur)
-        need = int(lib.hbmr_kmeans_bound_workspace_bytes(N, B, img.k))
-        bws = scratch.get("bound_ws")
-        if bws is None or bws.numel() < need:
-            bws = scratch["bound_ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
-    P = ctypes.c_void_p * B
-    cn, cmax, ce, cemax = norms
+        order_after(bases, ("g", "gap", "ref"), cur)
+        need = int(lib.hbmr_kmeans_bound_workspace_bytes(rb.N, rb.B, img.k))
+        bws = scratch_buf(rb.scratch, "bound_ws", need, torch.uint8, rb.dev)
+    P = ctypes.c_void_p * rb.B
+    cn, cmax, ce, cemax = rb.norms
     # the gaps are rewritten for THIS batch's labels from here on: they bound
     # nothing about ``g`` until it has advanced to those labels
     # (Baseline.labels_advanced), and nothing at all if that never happens
@@ -659,103 +712,65 @@ def _bounded_group(group, bases, img, labels_ptr, ch, norms, dt, scratch, stream
     for b in bases:
         b.ref = b.pending = None
     rc = lib.hbmr_kmeans_assign_top3_q1_bounded(
-        B, P(*[sp.xb.data_ptr() for sp in group]), (ctypes.c_long * B)(*ns), img.dp,
-        int(dt == torch.float16), _ptr(img.image16_tiled(dt)), _ptr(ch), img.k_pad, labels_ptr,
-        P(*[sp.xnorm.data_ptr() for sp in group]), P(*[sp.xbn2.data_ptr() for sp in group]),
-        P(*[sp.xerr.data_ptr() for sp in group]), img.d, img.k, _ptr(cn), _ptr(cmax), _ptr(ce),
-        _ptr(cemax), _ptr(rb.ws), rb.ws.numel(), _ptr(rb.pd),
+        rb.B, rb.xb, rb.ns, img.dp, int(rb.dt == torch.float16), ptr(img.image16_tiled(rb.dt)),
+        ptr(rb.ch), img.k_pad, labels_ptr, rb.xnorm, rb.xbn2, rb.xerr, img.d, img.k, ptr(cn),
+        ptr(cmax), ptr(ce), ptr(cemax), ptr(rb.ws), rb.ws.numel(), ptr(rb.pd),
         P(*[b.g.data_ptr() for b in bases]), P(*[b.gap.data_ptr() for b in bases]),
-        P(*[None if r is None else r.data_ptr() for r in refs]), _ptr(img.cen),
-        _ptr(bws), bws.numel(), _ptr(skipped), st)
+        P(*[ptr(r) for r in refs]), ptr(img.cen), ptr(bws), bws.numel(), ptr(skipped), rb.st)
     _lib.check(rc, "hbmr_kmeans_assign_top3_q1_bounded")
     for b in bases:
         b.pending = newref
 
 
-def _exact_group(group, img, stats, labels_ptr, c16, ch, norms, dt, scratch, stream, lib, st,
-                 bases=None, skipped=None, newref=None):
-    """Top-3 assign and certification of up to 64 splits with grouped launches
-    (hbmr_kmeans_assign_top3_grouped, hbmr_kmeans_refine_batch_q1g); labels of
-    the group written back to back at ``labels_ptr``.  Returns the row count."""
-    B = len(group)
-    ns = [sp.shape[0] for sp in group]
-    N = sum(ns)
-    dev = group[0].xb.device
-    P = ctypes.c_void_p * B
-    xs = P(*[sp.xb.data_ptr() for sp in group])
-    nsa = (ctypes.c_long * B)(*ns)
+def _exact_group(rb: _RefineBatch, labels_ptr: int, bases=None, skipped=None, newref=None):
+    """Top-3 assign and certification of up to 64 splits with grouped launches;
+    labels of the group written back to back at ``labels_ptr``.  Step 1 runs
+    in the top-3 kernel's epilogue (bounded: hbmr_kmeans_assign_top3_q1_bounded,
+    or hbmr_kmeans_assign_top3_q1_grouped: no candidate / score / margin
+    arrays), or as hbmr_kmeans_assign_top3_grouped + hbmr_kmeans_refine_batch_q1g."""
+    img, lib, st = rb.img, rb.lib, rb.st
+    f16 = int(rb.dt == torch.float16)
+    fused = bases is not None or (FUSED_Q1 and img.dp <= 128)
+    if not fused:
+        # launched before the certification's inputs are waited for (``open``)
+        cand, sc, mg = _top3_scratch(rb.scratch, "exact-group", rb.N, rb.dev)
+        rc = lib.hbmr_kmeans_assign_top3_grouped(
+            rb.B, rb.xb, rb.ns, img.dp, f16, ptr(rb.c16), ptr(rb.ch), img.k_pad, labels_ptr,
+            ptr(cand), ptr(sc), ptr(mg), st)
+        _lib.check(rc, "hbmr_kmeans_assign_top3_grouped")
+    rb.open()
+    cn, cmax, ce, cemax = rb.norms
+    if fused and TRACE.on:
+        TRACE.instant("kmeans.top3_launch", n=rb.B)
     if bases is not None:
-        rb = _RefineBatch(group, img, stats, scratch, stream)
-        if TRACE.on:
-            TRACE.instant("kmeans.top3_launch", n=B)
-        _bounded_group(group, bases, img, labels_ptr, ch, norms, dt, scratch, stream, lib, st, rb,
-                       skipped, newref)
-        o = 0
-        for i in range(B):
-            rb.labels[i] = labels_ptr + 4 * o
-            o += ns[i]
-        rb.finish()
-        return N
-    if FUSED_Q1 and img.dp <= 128:
-        # step 1 in the top-3 epilogue: no candidate / score / margin arrays
-        rb = _RefineBatch(group, img, stats, scratch, stream)
-        if TRACE.on:
-            TRACE.instant("kmeans.top3_launch", n=B)
-        cn, cmax, ce, cemax = norms
+        _bounded_group(rb, bases, labels_ptr, skipped, newref)
+    elif fused:
         rc = lib.hbmr_kmeans_assign_top3_q1_grouped(
-            B, xs, nsa, img.dp, int(dt == torch.float16), _ptr(c16),
-            _ptr(img.image16_tiled(dt)), _ptr(ch), img.k_pad,
-            labels_ptr, P(*[sp.xnorm.data_ptr() for sp in group]),
-            P(*[sp.xbn2.data_ptr() for sp in group]), P(*[sp.xerr.data_ptr() for sp in group]),
-            img.d, img.k, _ptr(cn), _ptr(cmax), _ptr(ce), _ptr(cemax), _ptr(rb.ws),
-            rb.ws.numel(), _ptr(rb.pd), st)
+            rb.B, rb.xb, rb.ns, img.dp, f16, ptr(rb.c16), ptr(img.image16_tiled(rb.dt)),
+            ptr(rb.ch), img.k_pad, labels_ptr, rb.xnorm, rb.xbn2, rb.xerr, img.d, img.k, ptr(cn),
+            ptr(cmax), ptr(ce), ptr(cemax), ptr(rb.ws), rb.ws.numel(), ptr(rb.pd), st)
         _lib.check(rc, "hbmr_kmeans_assign_top3_q1_grouped")
-        o = 0
-        for i in range(B):
-            rb.labels[i] = labels_ptr + 4 * o
-            o += ns[i]
-        rb.finish()
-        return N
-    key = ("exact-group", N)
-    bufs = scratch.get(key)
-    if bufs is None:
-        for kk in [kk for kk in scratch if isinstance(kk, tuple) and kk[0] == "exact-group"]:
-            del scratch[kk]
-        bufs = scratch[key] = (torch.empty(2 * N, dtype=torch.int32, device=dev),
-                               torch.empty(N, dtype=torch.float32, device=dev),
-                               torch.empty(2 * N, dtype=torch.float32, device=dev))
-    cand, sc, mg = bufs
-    rc = lib.hbmr_kmeans_assign_top3_grouped(B, xs, nsa, img.dp, int(dt == torch.float16),
-                                             _ptr(c16), _ptr(ch), img.k_pad, labels_ptr,
-                                             _ptr(cand), _ptr(sc), _ptr(mg), st)
-    _lib.check(rc, "hbmr_kmeans_assign_top3_grouped")
-    rb = _RefineBatch(group, img, stats, scratch, stream)
-    cn, cmax, ce, cemax = norms
-    rc = lib.hbmr_kmeans_refine_batch_q1g(
-        B, nsa, img.d, img.k, img.k_pad, P(*[sp.xnorm.data_ptr() for sp in group]),
-        P(*[sp.xbn2.data_ptr() for sp in group]), P(*[sp.xerr.data_ptr() for sp in group]),
-        _ptr(cn), _ptr(cmax), _ptr(ce), _ptr(cemax), labels_ptr, _ptr(cand), _ptr(sc), _ptr(mg),
-        _ptr(rb.ws), rb.ws.numel(), _ptr(rb.pd), st)
-    _lib.check(rc, "hbmr_kmeans_refine_batch_q1g")
-    o = 0
-    for i in range(B):
-        rb.labels[i] = labels_ptr + 4 * o
-        o += ns[i]
+    else:
+        rc = lib.hbmr_kmeans_refine_batch_q1g(
+            rb.B, rb.ns, img.d, img.k, img.k_pad, rb.xnorm, rb.xbn2, rb.xerr, ptr(cn), ptr(cmax),
+            ptr(ce), ptr(cemax), labels_ptr, ptr(cand), ptr(sc), ptr(mg), ptr(rb.ws), rb.ws.numel(),
+            ptr(rb.pd), st)
+        _lib.check(rc, "hbmr_kmeans_refine_batch_q1g")
+    rb.labels_at(labels_ptr)
     rb.finish()
-    return N
 
 
 def map_split_exact(split: ExactSplit, img: CentroidImage, sums, counts, scratch: dict,
-                    stats: torch.Tensor, stream=None) -> None:
+                    stats: torch.Tensor, stream=None) -> torch.Tensor:
     """One exact-mode GPU map task: top-3 assign, certification + fp64 re-score,
-    then the int64 fixed-point combiner over the fp32 rows."""
-    n = split.shape[0]
+    then the int64 fixed-point combiner over the fp32 rows.  Returns the
+    labels (a view of ``scratch``, as ``assign_exact``'s)."""
     lab = assign_exact(split, img, stats, scratch, stream=stream)
-    need = workspace_bytes(n, img.k)
-    if scratch.get("ws") is None or scratch["ws"].numel() < need:
-        scratch["ws"] = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=split.xb.device)
+    ws = scratch_buf(scratch, "ws", workspace_bytes(split.shape[0], img.k), torch.uint8,
+                     split.xb.device, floor=1 << 20)
     accumulate(split.x32, lab, img.k, sums, counts, fx_shift=img.fx_shift, stream=stream,
-               workspace=scratch["ws"])
+               workspace=ws)
+    return lab
 
 
 def map_batch_gpu(splits: list, img: CentroidImage, sums: torch.Tensor, counts: torch.Tensor,
@@ -766,9 +781,7 @@ def map_batch_gpu(splits: list, img: CentroidImage, sums: torch.Tensor, counts: 
     B = len(splits)
     if B == 0:
         return
-    for s in splits:
-        if s.dtype != torch.bfloat16 or s.shape[1] != img.dp or not s.is_contiguous():
-            raise ValueError("splits must be contiguous bf16 [n, dp]")
+    _check_rows(splits, img.dp, (torch.bfloat16,))
     if sums.shape != (B, img.k, img.dp) or counts.shape != (B, img.k):
         raise ValueError("batch output shape mismatch")
     need_lab, need_ws = batch_scratch_sizes([s.shape[0] for s in splits], img.k)
@@ -779,9 +792,9 @@ def map_batch_gpu(splits: list, img: CentroidImage, sums: torch.Tensor, counts: 
         raise ValueError("workspace too small")
     ptrs = (ctypes.c_void_p * B)(*[s.data_ptr() for s in splits])
     ns = (ctypes.c_long * B)(*[s.shape[0] for s in splits])
-    rc = lib.hbmr_kmeans_map_batch(B, ptrs, ns, img.dp, _ptr(img.cbf), _ptr(img.chalf), img.k_pad,
-                                   img.k, _ptr(labels), _ptr(workspace), workspace.numel(),
-                                   _ptr(sums), _ptr(counts), img.fx_shift, int(zero_outputs),
+    rc = lib.hbmr_kmeans_map_batch(B, ptrs, ns, img.dp, ptr(img.cbf), ptr(img.chalf), img.k_pad,
+                                   img.k, ptr(labels), ptr(workspace), workspace.numel(),
+                                   ptr(sums), ptr(counts), img.fx_shift, int(zero_outputs),
                                    _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_kmeans_map_batch")
 
@@ -829,29 +842,15 @@ def delta_workspace_bytes(total: int, ntasks: int, k: int) -> int:
 
 
 def _delta_args(xs, bases, stream):
+    """The delta kernels' tables over a batch (rows, sizes, g, S0, N0), with
+    the batch ordered behind its reference partitions (``order_after``)."""
     B = len(xs)
-    st = torch.cuda.current_stream() if stream is None else stream
-    events, blocks = {}, {}
-    for b in bases:
-        # the reference partition may have been written (g) / allocated (S0, N0)
-        # on another stream: order this batch after it, and keep the memory from
-        # being reused under this stream's pending reads (once per event and
-        # per allocation: the baselines of a batch share a few slabs)
-        if b.event is not None and b.stream is not None and b.stream != st:
-            events[id(b.event)] = b.event
-        for t in (b.g, b.S0, b.N0):
-            base = t._base if t._base is not None else t
-            blocks[id(base)] = base
-    for ev in events.values():
-        st.wait_event(ev)
-    for t in blocks.values():
-        t.record_stream(st)
-    ptrs = (ctypes.c_void_p * B)(*[x.data_ptr() for x in xs])
-    ns = (ctypes.c_long * B)(*[x.shape[0] for x in xs])
-    gs = (ctypes.c_void_p * B)(*[b.g.data_ptr() for b in bases])
-    s0 = (ctypes.c_void_p * B)(*[b.S0.data_ptr() for b in bases])
-    n0 = (ctypes.c_void_p * B)(*[b.N0.data_ptr() for b in bases])
-    return ptrs, ns, gs, s0, n0
+    order_after(bases, ("g", "S0", "N0"),
+                torch.cuda.current_stream() if stream is None else stream)
+    P = ctypes.c_void_p * B
+    return (P(*[x.data_ptr() for x in xs]), (ctypes.c_long * B)(*[x.shape[0] for x in xs]),
+            P(*[b.g.data_ptr() for b in bases]), P(*[b.S0.data_ptr() for b in bases]),
+            P(*[b.N0.data_ptr() for b in bases]))
 
 
 def map_batch_delta(splits: list, img: CentroidImage, sums: torch.Tensor, counts: torch.Tensor,
@@ -865,9 +864,8 @@ def map_batch_delta(splits: list, img: CentroidImage, sums: torch.Tensor, counts
         return
     if B > 64 or len(bases) != B:
         raise ValueError("at most 64 splits per delta batch, one baseline each")
+    _check_rows(splits, img.dp, (torch.bfloat16,))
     for s, b in zip(splits, bases):
-        if s.dtype != torch.bfloat16 or s.shape[1] != img.dp or not s.is_contiguous():
-            raise ValueError("splits must be contiguous bf16 [n, dp]")
         if b.g.numel() != s.shape[0] or tuple(b.S0.shape) != (img.k, img.dp) or \
                 b.N0.numel() != img.k:
             raise ValueError("baseline does not match its split")
@@ -884,8 +882,8 @@ def map_batch_delta(splits: list, img: CentroidImage, sums: torch.Tensor, counts
     for b in bases:
         b.labels_advanced()           # exact mode's bounds, if any, were for other labels
     rc = _lib.load().hbmr_kmeans_map_batch_delta(
-        B, ptrs, ns, img.dp, _ptr(img.cbf), _ptr(img.chalf), img.k_pad, img.k, _ptr(labels),
-        _ptr(workspace), workspace.numel(), _ptr(sums), _ptr(counts), img.fx_shift, gs, s0, n0,
+        B, ptrs, ns, img.dp, ptr(img.cbf), ptr(img.chalf), img.k_pad, img.k, ptr(labels),
+        ptr(workspace), workspace.numel(), ptr(sums), ptr(counts), img.fx_shift, gs, s0, n0,
         _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_kmeans_map_batch_delta")
 
@@ -906,11 +904,9 @@ def delta_combine(xs: list, labels: torch.Tensor, k: int, sums: torch.Tensor,
     for b in bases:
         b.labels_advanced()
     dp = xs[0].shape[1]
-    f32 = xs[0].dtype == torch.float32
-    for x, b in zip(xs, bases):
-        if x.dtype != xs[0].dtype or x.shape[1] != dp or not x.is_contiguous() or \
-                b.g.numel() != x.shape[0]:
-            raise ValueError("delta_combine: rows/baselines mismatch")
+    _check_rows(xs, dp)
+    if any(b.g.numel() != x.shape[0] for x, b in zip(xs, bases)):
+        raise ValueError("delta_combine: rows/baselines mismatch")
     if B > 64 or dp not in SUPPORTED_DP or sums.shape != (B, k, dp) or counts.shape != (B, k):
         raise ValueError("delta_combine: shape mismatch")
     total = sum(x.shape[0] for x in xs)
@@ -919,8 +915,9 @@ def delta_combine(xs: list, labels: torch.Tensor, k: int, sums: torch.Tensor,
         raise ValueError("delta_combine: scratch too small")
     ptrs, ns, gs, s0, n0 = _delta_args(xs, bases, stream)
     rc = _lib.load().hbmr_kmeans_delta_combine(
-        B, ptrs, ns, dp, int(f32), k, _ptr(labels), _ptr(workspace), workspace.numel(),
-        _ptr(sums), _ptr(counts), fx_shift, gs, s0, n0, _lib.stream_handle(stream))
+        B, ptrs, ns, dp, int(xs[0].dtype == torch.float32), k, ptr(labels), ptr(workspace),
+        workspace.numel(), ptr(sums), ptr(counts), fx_shift, gs, s0, n0,
+        _lib.stream_handle(stream))
     _lib.check(rc, "hbmr_kmeans_delta_combine")
     if keep_bounds:
         for b, p in zip(bases, pend):
@@ -956,8 +953,8 @@ def map_split_cpu(points: torch.Tensor, centroids: torch.Tensor, sums: torch.Ten
     cost = ctypes.c_double(0.0)
     lib = _lib.load()
     res = ctypes.c_long(0)
-    rc = lib.hbmr_kmeans_map_cpu_f32_ex(_ptr(x), n, d, _ptr(c), k, _ptr(labels), _ptr(target),
-                                        _ptr(counts), ctypes.byref(cost), fx_shift, int(nthreads),
+    rc = lib.hbmr_kmeans_map_cpu_f32_ex(ptr(x), n, d, ptr(c), k, ptr(labels), ptr(target),
+                                        ptr(counts), ctypes.byref(cost), fx_shift, int(nthreads),
                                         int(exact), ctypes.byref(res))
     _lib.check(rc, "hbmr_kmeans_map_cpu_f32_ex")
     if stats is not None:
