@@ -18,12 +18,15 @@ from __future__ import annotations
 
 import argparse
 import hashlib
+import logging
 import os
 
 from ..io import sequencefile as seqf
 from ..mapred import FileInputFormat, JobClient, JobConf
 from ..mapred.api import Mapper
 from ..mapred.formats import NullOutputFormat, SequenceFileInputFormat, SequenceFileRecordReader
+
+log = logging.getLogger("hbmr.benchmarks.sortvalidator")
 
 GROUP = "SortValidator"
 M64 = (1 << 64) - 1
@@ -88,10 +91,27 @@ class ValidateMapper(Mapper):
                 reporter.incrCounter(GROUP, "MISPARTITIONED_RECORDS", 1)
 
 
-def validate(sort_input, sort_output, conf=None, cluster=None, total_order=False) -> dict:
-    """Run the checks; returns {'ok': bool, ...counts}."""
-    job = JobConf(conf)
+def _validate_gpu(sort_input, sort_output, conf, cluster, total_order):
+    """The checks as a split job; None if the directories are not eligible (the
+    reason is logged)."""
+    from ..examples._gpu import run_gpu_job
+    from ..models import sortvalidate as V
+    return run_gpu_job(lambda: V.gpu_job(sort_input, sort_output, total_order, base=conf),
+                       "sortvalidate", conf, cluster, log)
+
+
+def validate(sort_input, sort_output, conf=None, cluster=None, total_order=False,
+             gpu=False) -> dict:
+    """Run the checks; returns {'ok': bool, ...counts}.  ``gpu``: as the map-only
+    split-level job of hbmr/models/sortvalidate.py, the classic job if the
+    directories are not eligible (the reason is logged)."""
     outs = sorted(p for p in os.listdir(sort_output) if p.startswith("part-"))
+    rj = _validate_gpu(sort_input, sort_output, conf, cluster, total_order) if gpu else None
+    if rj is not None:
+        from ..models.sortvalidate import range_overlaps
+        return _result(rj.getCounters(), total_order,
+                       lambda: range_overlaps(sort_output, outs), M64)
+    job = JobConf(conf)
     job.set_job_name("sortvalidate")
     job.set("sortvalidate.sorted.dir", sort_output)
     job.set_int("sortvalidate.reduces", len(outs))
@@ -102,17 +122,21 @@ def validate(sort_input, sort_output, conf=None, cluster=None, total_order=False
     job.set_num_reduce_tasks(0)
     job.set_output_format(NullOutputFormat)
     rj = JobClient.runJob(job, cluster=cluster, verbose=False)
-    cs = rj.getCounters()
+    return _result(rj.getCounters(), total_order, lambda: _range_overlaps(sort_output, outs))
 
+
+def _result(cs, total_order, overlaps, sum_mask=-1) -> dict:
+    """``sum_mask``: the split job's maps add per-split sums mod 2^64, so its
+    HASH_SUM counters compare mod 2^64 too."""
     def c(n):
         return cs.get(GROUP, n)
 
     res = {k: c(k) for k in ("IN_RECORDS", "OUT_RECORDS", "IN_BYTES", "OUT_BYTES",
                              "UNSORTED_RECORDS", "MISPARTITIONED_RECORDS")}
-    res["checksum_match"] = (c("IN_HASH_SUM") == c("OUT_HASH_SUM") and
+    res["checksum_match"] = ((c("IN_HASH_SUM") & sum_mask) == (c("OUT_HASH_SUM") & sum_mask) and
                              (c("IN_HASH_SQ_SUM") & M64) == (c("OUT_HASH_SQ_SUM") & M64))
     if total_order:  # partitions must hold contiguous, increasing key ranges
-        res["RANGE_OVERLAPS"] = _range_overlaps(sort_output, outs)
+        res["RANGE_OVERLAPS"] = overlaps()
     res["ok"] = (res["IN_RECORDS"] == res["OUT_RECORDS"] and res["IN_BYTES"] == res["OUT_BYTES"]
                  and res["checksum_match"] and res["UNSORTED_RECORDS"] == 0
                  and res["MISPARTITIONED_RECORDS"] == 0 and res.get("RANGE_OVERLAPS", 0) == 0)
@@ -143,8 +167,11 @@ def main(argv=None, cluster=None):
     ap.add_argument("-sortInput", required=True)
     ap.add_argument("-sortOutput", required=True)
     ap.add_argument("-totalOrder", action="store_true")
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a map-only split-level job (record digest kernels on GPU slots)")
     a = ap.parse_args(argv)
-    res = validate(a.sortInput, a.sortOutput, cluster=cluster, total_order=a.totalOrder)
+    res = validate(a.sortInput, a.sortOutput, cluster=cluster, total_order=a.totalOrder,
+                   gpu=a.gpu)
     print(("SUCCESS! Validated the MapReduce framework's 'sort' successfully."
            if res["ok"] else f"FAILED: {res}"))
     return 0 if res["ok"] else 1

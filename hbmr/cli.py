@@ -19,6 +19,7 @@ jar/pipes/job/fs/version/... dispatch).
   hbmr distch [-i] PATH:OWNER:GROUP:PERM ...  |  hbmr failmon [--interval S] [--logs GLOB..]
   hbmr gridmix [-generate BYTES] [-jobtype LOADJOB|SLEEPJOB] [-policy REPLAY|STRESS|SERIAL] IOPATH TRACE
   hbmr test TestDFSIO|nnbench|mrbench|testbigmapoutput|threadedmapbench|sortvalidate ...
+            (sortvalidate -sortInput I -sortOutput O [-totalOrder] [-gpu])
   hbmr node            start this process's TaskTracker (+ JobTracker on rank 0)
                        under torchrun: one process per GPU
   hbmr run module:function [args]     run a user program (the ``jar`` analogue)

@@ -204,6 +204,9 @@ _SIGS = {
                                     c_void_p]),
     "hbmr_recjoin_copy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long,
                                   c_void_p, c_void_p]),
+    # record validation (native/kernels/recvalidate.hip)
+    "hbmr_recvalidate_digest": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_recvalidate_order": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -289,6 +289,14 @@ int hbmr_recjoin_frames(const int64_t* tab, int S, const int32_t* mask, const in
 int hbmr_recjoin_copy(const int64_t* psrc, const int64_t* plen, const int64_t* pdst,
                       const int64_t* chunk_base, const uint32_t* chunk_entry, long nchunks,
                       uint8_t* dst, hipStream_t st);
+// ---- record validation (native/kernels/recvalidate.hip) ----------------------
+// out[4]: records, sum(flen - 8), sum h, sum h^2 (mod 2^64) of the frames, h the
+// frame digest of hbmr/ops/recvalidate.py
+int hbmr_recvalidate_digest(const uint8_t* data, const int64_t* foff, const int64_t* flen, long n,
+                            uint64_t* out, hipStream_t st);
+// *unsorted: the records whose key payload is below their predecessor's
+int hbmr_recvalidate_order(const uint8_t* data, const int64_t* koff, const int64_t* klen, long n,
+                           uint64_t* unsorted, hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
