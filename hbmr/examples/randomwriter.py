@@ -6,17 +6,27 @@ SequenceFile.
 RandomWriter: BytesWritable keys/values, lengths uniform in
 [min_key, max_key] / [min_value, max_value] (test.randomwrite.{min,max}_{key,value}).
 RandomTextWriter: Text keys/values of random words from a fixed vocabulary.
+
+``-gpu`` runs either as the split-level job of hbmr/models/randomwrite.py
+(record generator kernels on the GPU map slots; records of the same shape that
+depend only on ``-seed``, map and record number, and parts that stay in HBM for
+``sort -gpu`` and ``sortvalidate -gpu``).  A job it does not take logs the
+reason and runs the classic job.
 """
 from __future__ import annotations
 
 import argparse
+import logging
 import random
 
 from ..io.writable import BytesWritable, Text
 from ..mapred import FileOutputFormat, JobClient, JobConf
 from ..mapred.api import InputFormat, Mapper, RecordReader
 from ..mapred.formats import SequenceFileOutputFormat
+from ._gpu import run_gpu_job
 from .sleepjob import EmptySplit
+
+log = logging.getLogger("hbmr.examples.randomwriter")
 
 
 class _CounterReader(RecordReader):
@@ -111,15 +121,40 @@ def make_job(out, maps=2, bytes_per_map=1 << 20, text=False, conf=None) -> JobCo
     return job
 
 
-def main(argv=None, cluster=None, text=False):
+def run(out, maps=2, bytes_per_map=1 << 20, text=False, seed=0, conf=None, cluster=None,
+        gpu=False):
+    """Run the job; ``gpu``: as the split-level job of hbmr/models/randomwrite.py
+    (record generator kernels on the GPU map slots, records that depend on
+    ``seed`` alone), the classic job if it does not take the job (the reason is
+    logged).  Record bounds under which no record ever adds a byte raise
+    ValueError there; the classic job would not end."""
+    rj = None
+    if gpu:
+        from ..models import randomwrite as W
+        from ..ops import recgen
+        base = JobConf(conf)
+        recgen.check_params(recgen.TEXT if text else recgen.BYTES, W.record_params(base, text)[1])
+        rj = run_gpu_job(lambda: W.gpu_job(out, maps, bytes_per_map, text, seed, base=conf),
+                         "randomtextwriter" if text else "randomwriter", conf, cluster, log)
+    if rj is None:
+        rj = JobClient.runJob(make_job(out, maps, bytes_per_map, text, conf), cluster=cluster)
+    return rj
+
+
+def main(argv=None, cluster=None, text=False, conf=None):
     ap = argparse.ArgumentParser(prog="hbmr randomtextwriter" if text else "hbmr randomwriter")
     ap.add_argument("outdir")
     ap.add_argument("-m", "--maps", type=int, default=2)
     ap.add_argument("-b", "--bytes-per-map", type=int, default=1 << 20)
+    ap.add_argument("-seed", type=int, default=None,
+                    help="hbmr.randomwrite.seed: the records of the -gpu job depend on it alone")
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a split-level job (record generator kernels on GPU slots)")
     a = ap.parse_args(argv)
-    rj = JobClient.runJob(make_job(a.outdir, a.maps, a.bytes_per_map, text), cluster=cluster)
+    seed = a.seed if a.seed is not None else JobConf(conf).get_long("hbmr.randomwrite.seed", 0)
+    rj = run(a.outdir, a.maps, a.bytes_per_map, text, seed, conf, cluster, a.gpu)
     return 0 if rj.isSuccessful() else 1
 
 
-def main_text(argv=None, cluster=None):
-    return main(argv, cluster, text=True)
+def main_text(argv=None, cluster=None, conf=None):
+    return main(argv, cluster, text=True, conf=conf)

@@ -207,6 +207,15 @@ _SIGS = {
     # record validation (native/kernels/recvalidate.hip)
     "hbmr_recvalidate_digest": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_recvalidate_order": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    # record generator (native/kernels/recgen.hip)
+    "hbmr_recgen_chunk_bytes": (c_int, []),
+    "hbmr_recgen_lengths": (c_int, [c_uint64, c_long, c_long, c_int, c_uint, c_uint, c_uint,
+                                    c_uint, c_void_p, c_int, c_void_p, c_void_p]),
+    "hbmr_recgen_fill_bytes": (c_int, [c_uint64, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    "hbmr_recgen_fill_text": (c_int, [c_uint64, c_long, c_long, c_uint, c_uint, c_uint, c_uint,
+                                      c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -322,14 +322,16 @@ def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None):
     return perm, part_records
 
 
-def _chunk_table(dst_off, lens, out, skip_empty=False):
+def _chunk_table(dst_off, lens, out, skip_empty=False, chunk=None):
     """(base int64[n + 1], entry int32[total], total): the chunk table of a copy
     of n runs of ``lens`` bytes to the offsets ``dst_off`` of ``out``.  A run is
-    cut into chunks of hbmr_recsort_chunk_bytes() bytes counted from the 16-byte
-    boundary below its first byte in memory; ``base`` is the exclusive scan of
-    the chunks per run, ``entry`` the run of each chunk.  ``skip_empty``: an
-    empty run gets no chunk (else one if it starts off a boundary)."""
-    chunk = int(_lib.load().hbmr_recsort_chunk_bytes())
+    cut into chunks of ``chunk`` bytes (hbmr_recsort_chunk_bytes() if None)
+    counted from the 16-byte boundary below its first byte in memory; ``base`` is
+    the exclusive scan of the chunks per run, ``entry`` the run of each chunk.
+    ``skip_empty``: an empty run gets no chunk (else one if it starts off a
+    boundary)."""
+    if chunk is None:
+        chunk = int(_lib.load().hbmr_recsort_chunk_bytes())
     n = int(lens.numel())
     nch = (((dst_off + out.data_ptr()) & 15) + lens + (chunk - 1)) // chunk
     if skip_empty:

@@ -297,6 +297,22 @@ int hbmr_recvalidate_digest(const uint8_t* data, const int64_t* foff, const int6
 // *unsorted: the records whose key payload is below their predecessor's
 int hbmr_recvalidate_order(const uint8_t* data, const int64_t* koff, const int64_t* klen, long n,
                            uint64_t* unsorted, hipStream_t st);
+// ---- record generator (native/kernels/recgen.hip) -----------------------------
+// RandomWriter's and RandomTextWriter's records as hbmr/ops/recgen.py defines
+// them; S is the split word of (seed, map).  out[4][count]: key and value payload
+// lengths and (text) word counts
+int hbmr_recgen_chunk_bytes(void);
+int hbmr_recgen_lengths(uint64_t S, long first, long count, int text, uint32_t lo_k,
+                        uint32_t range_k, uint32_t lo_v, uint32_t range_v, const int32_t* woff,
+                        int nwords, int64_t* out, hipStream_t st);
+int hbmr_recgen_fill_bytes(uint64_t S, long first, const int64_t* foff, const int64_t* flen,
+                           const int64_t* klen, const int64_t* chunk_base,
+                           const uint32_t* chunk_entry, long n, long nchunks, uint8_t* dst,
+                           hipStream_t st);
+int hbmr_recgen_fill_text(uint64_t S, long first, long n, uint32_t lo_k, uint32_t range_k,
+                          uint32_t lo_v, uint32_t range_v, const uint8_t* blob,
+                          const int32_t* woff, int nwords, int nbytes, const int64_t* foff,
+                          const int64_t* flen, const int64_t* klen, uint8_t* dst, hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);

@@ -1,8 +1,9 @@
 #pragma once
-// Byte-string records in HBM, shared by recsort.hip and recjoin.hip: the round
-// key and the compare of key payloads (WritableComparator.compareBytes:
-// unsigned bytes, a proper prefix first) and the slot copy of the two
-// variable-length copies.
+// Byte-string records in HBM, shared by recsort.hip, recjoin.hip,
+// recvalidate.hip and recgen.hip: the round key and the compare of key payloads
+// (WritableComparator.compareBytes: unsigned bytes, a proper prefix first), the
+// splitmix64 finaliser, and the destination-aligned slots of the two
+// variable-length copies and of the record fill.
 #include "../common.h"
 
 namespace {
@@ -35,11 +36,34 @@ __device__ __forceinline__ int compare_from(const uint8_t* a, long la, const uin
   return la < lb ? -1 : (la > lb ? 1 : 0);
 }
 
+// the splitmix64 finaliser: the record digest's word hash and the record
+// generator's counter hash
+__device__ __forceinline__ uint64_t mix64(uint64_t x) {
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
 constexpr int kCopyLanes = 16;                 // lanes per copy chunk
 constexpr int kCopyChunk = kCopyLanes * 16;    // bytes of a chunk: 16 slots of 16 bytes
 
-// Lane `lane` of chunk c of the run dst[a, end) copies its slot.  The run is
-// cut into chunks of 16 of its DESTINATION-aligned 16-byte slots: a full slot
+// The run dst[a, end) is cut into chunks of 16 of its DESTINATION-aligned
+// 16-byte slots.  Slot `lane` of chunk c begins at offset `slot` of dst (a
+// multiple of 16 in memory; below a for the run's first slot) and holds the
+// run's bytes [b, e); false if it holds none.
+__device__ __forceinline__ bool slot_span(const uint8_t* dst, long a, long end, long c, int lane,
+                                          long& slot, long& b, long& e) {
+  const long mis = (long)(reinterpret_cast<uintptr_t>(dst + a) & 15);
+  slot = a - mis + c * kCopyChunk + lane * 16L;
+  b = slot > a ? slot : a;
+  e = slot + 16 < end ? slot + 16 : end;
+  return b < e;
+}
+
+// Lane `lane` of chunk c of the run dst[a, end) copies its slot: a full slot
 // is one 16-byte load (at whatever alignment the source has) and one aligned
 // 16-byte store, the partial slots at the run's head and tail go bytewise.
 // src_of_a() gives the source address of byte a; it is asked only by a lane
@@ -47,11 +71,8 @@ constexpr int kCopyChunk = kCopyLanes * 16;    // bytes of a chunk: 16 slots of 
 template <class Src>
 __device__ __forceinline__ void copy_slot(uint8_t* __restrict__ dst, long a, long end, long c,
                                           int lane, Src src_of_a) {
-  const long mis = (long)(reinterpret_cast<uintptr_t>(dst + a) & 15);
-  const long slot = a - mis + c * kCopyChunk + lane * 16L;
-  long b = slot > a ? slot : a;
-  const long e = slot + 16 < end ? slot + 16 : end;
-  if (b >= e) return;
+  long slot, b, e;
+  if (!slot_span(dst, a, end, c, lane, slot, b, e)) return;
   const uint8_t* q = src_of_a() + (b - a);
   if (e - b == 16) {
     uint4 v;

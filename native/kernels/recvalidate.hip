@@ -41,17 +41,8 @@ constexpr int kMaxBlocks = 4096;              // the groups stride over the reco
 constexpr uint64_t kWordMul = 0x9E3779B97F4A7C15ull;
 constexpr uint64_t kLenMul = 0xD6E8FEB86659FD93ull;
 
-__device__ __forceinline__ uint64_t mix(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27;
-  x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return x;
-}
-
 __device__ __forceinline__ uint64_t word_hash(uint64_t w, long j) {
-  return mix(w + (uint64_t)(j + 1) * kWordMul);
+  return mix64(w + (uint64_t)(j + 1) * kWordMul);
 }
 
 // sum of v over the workgroup, in thread 0; s_w: one uint64 per wave
@@ -119,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void recvalidate_digest_kernel(
 #pragma unroll
     for (int d = kLanes / 2; d > 0; d >>= 1) s += __shfl_xor(s, d, kLanes);
     if (lane == 0) {
-      const uint64_t h = mix(s ^ ((uint64_t)len * kLenMul));
+      const uint64_t h = mix64(s ^ ((uint64_t)len * kLenMul));
       tot[0] += 1;
       tot[1] += (uint64_t)(len - 8);
       tot[2] += h;
