@@ -1,15 +1,24 @@
 """SecondarySort (src/examples/org/apache/hadoop/examples/SecondarySort.java):
 input lines "a b" (two ints); keys are IntPair(a, b) sorted by (a, b),
 partitioned and grouped by a only, so each reduce call sees one a with its b
-values in increasing order.  Output: a separator line, then "a b" lines."""
+values in increasing order.  Output: a separator line, then "a b" lines.
+
+``-gpu`` runs the job as the split-level job of hbmr/models/secondarysort.py
+(int-pair text kernels on the GPU map slots) with the same output, byte for
+byte.  An input the GPU job does not take logs the reason and runs the classic
+job."""
 from __future__ import annotations
 
 import argparse
+import logging
 import struct
 
 from ..io.writable import IntWritable, Text, WritableComparable
 from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf, Mapper, Reducer
 from ..mapred.api import Partitioner
+from ._gpu import run_gpu_job
+
+log = logging.getLogger("hbmr.examples.secondarysort")
 
 SEPARATOR = Text("------------------------------------------------")
 
@@ -92,10 +101,31 @@ def make_job(inp, out, reduces=1, conf=None) -> JobConf:
     return job
 
 
+def run(inp, out, reduces=1, conf=None, cluster=None, maps=None, gpu=False):
+    """Run the job; ``gpu``: as the split-level job of
+    hbmr/models/secondarysort.py, the classic job if the input is not eligible
+    (the reason is logged)."""
+    rj = None
+    if gpu:
+        from ..models import secondarysort as S
+        rj = run_gpu_job(lambda: S.gpu_job(inp, out, reduces, base=conf, maps=maps),
+                         "secondarysort", conf, cluster, log)
+    if rj is not None:
+        return rj
+    job = make_job(inp, out, reduces, conf)
+    if maps:
+        job.set_num_map_tasks(maps)
+    return JobClient.runJob(job, cluster=cluster)
+
+
 def main(argv=None, cluster=None):
     ap = argparse.ArgumentParser(prog="hbmr secondarysort")
     ap.add_argument("input")
     ap.add_argument("output")
+    ap.add_argument("-r", type=int, default=1, help="reduces")
+    ap.add_argument("-m", type=int, default=None, help="maps")
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a split-level job (int-pair text kernels on GPU slots)")
     a = ap.parse_args(argv)
-    rj = JobClient.runJob(make_job(a.input, a.output), cluster=cluster)
+    rj = run(a.input, a.output, a.r, cluster=cluster, maps=a.m, gpu=a.gpu)
     return 0 if rj.isSuccessful() else 1

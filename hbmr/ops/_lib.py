@@ -216,6 +216,18 @@ _SIGS = {
     "hbmr_recgen_fill_text": (c_int, [c_uint64, c_long, c_long, c_uint, c_uint, c_uint, c_uint,
                                       c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
+    # int-pair text (native/kernels/intpair.hip)
+    "hbmr_intpair_tiles": (c_long, [c_long]),
+    "hbmr_intpair_blocks": (c_long, [c_long]),
+    "hbmr_intpair_lines_count": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "hbmr_intpair_lines_write": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_intpair_parse": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p]),
+    "hbmr_intpair_compact": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                                     c_void_p]),
+    "hbmr_intpair_partition": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p]),
+    "hbmr_intpair_lengths": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_intpair_fill": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -313,6 +313,26 @@ int hbmr_recgen_fill_text(uint64_t S, long first, long n, uint32_t lo_k, uint32_
                           uint32_t lo_v, uint32_t range_v, const uint8_t* blob,
                           const int32_t* woff, int nwords, int nbytes, const int64_t* foff,
                           const int64_t* flen, const int64_t* klen, uint8_t* dst, hipStream_t st);
+// ---- int-pair text (native/kernels/intpair.hip) --------------------------------
+// SecondarySort's map and reduce as hbmr/ops/intpair.py defines them: the lines
+// of a text split parsed into IntPair key words, FirstPartitioner, and the
+// reduce output's text.  Buffers may have any alignment.
+long hbmr_intpair_tiles(long n);
+long hbmr_intpair_blocks(long n);
+int hbmr_intpair_lines_count(const uint8_t* buf, long n, uint32_t* tile_counts, int* non_ascii,
+                             hipStream_t st);
+int hbmr_intpair_lines_write(const uint8_t* buf, long n, const long* tile_base, long nlines,
+                             int32_t* starts, hipStream_t st);
+int hbmr_intpair_parse(const uint8_t* buf, long n, const int32_t* starts, long nlines,
+                       uint8_t* status, int64_t* keys, uint32_t* block_counts, int* irregular,
+                       hipStream_t st);
+int hbmr_intpair_compact(const uint8_t* status, const int64_t* keys, long nlines,
+                         const long* block_base, long nrecords, int64_t* out, hipStream_t st);
+int hbmr_intpair_partition(const int64_t* keys, long n, long nparts, int64_t* parts,
+                           hipStream_t st);
+int hbmr_intpair_lengths(const int64_t* keys, long n, int32_t* lens, hipStream_t st);
+int hbmr_intpair_fill(const int64_t* keys, const int64_t* offs, long n, uint8_t* dst,
+                      hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
