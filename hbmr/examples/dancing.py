@@ -5,16 +5,25 @@ distributed pentomino job (src/examples/org/apache/hadoop/examples/dancing/
 The distributed job enumerates the search tree to a fixed depth on the client,
 writes one prefix per input line (NLineInputFormat, one line per map) and each
 map counts the solutions below its prefix; a reducer sums them.
+
+``pentomino -gpu`` runs the count as the split-level job of
+hbmr/models/pentomino.py (exact-cover kernels on the GPU map slots, the same
+search in C++ on CPU slots) over the same prefixes, with the same
+``part-00000``; ``-onesided`` takes the 18 one-sided pentominoes
+(:class:`OneSidedPentomino`), on either path.
 """
 from __future__ import annotations
 
 import argparse
+import logging
 import os
 import tempfile
 
 from ..io.writable import LongWritable, Text
 from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf, Mapper, Reducer
 from ..mapred.formats import NLineInputFormat
+
+log = logging.getLogger("hbmr.examples.pentomino")
 
 
 class DancingLinks:
@@ -167,14 +176,17 @@ class Pentomino:
     distinct solution once, the X piece is restricted to the board's lower-left
     quadrant (removes the rotations/reflections of symmetric boards)."""
 
+    pieces = _PIECES
+    fixed = False          # True: rotations only (a mirror image is another piece)
+
     def __init__(self, width=10, height=6):
         self.w, self.h = width, height
-        names = sorted(_PIECES)
+        names = sorted(self.pieces)
         self.names = names
         ncols = len(names) + width * height
         self.dl = DancingLinks(ncols)
         for pi, name in enumerate(names):
-            for shape in _orientations(_PIECES[name]):
+            for shape in _orientations(self.pieces[name], fixed=self.fixed):
                 ph = max(r for r, _ in shape) + 1
                 pw = max(c for _, c in shape) + 1
                 for y in range(height - ph + 1):
@@ -193,10 +205,32 @@ class Pentomino:
         return self.dl.split(depth)
 
 
+_CHIRAL = "FLNPYZ"      # the shapes no rotation turns into their mirror image
+
+
+class OneSidedPentomino(Pentomino):
+    """The 18 one-sided pentominoes (pieces may be turned but not flipped over,
+    so each chiral shape comes in both mirror forms, ``F`` and ``F'``) on a
+    width×height board of 90 cells, e.g. 9×10.  Board columns and the X-piece
+    restriction are Pentomino's: the piece set is closed under reflection, so
+    the board's symmetries act on the solutions as they do there."""
+
+    pieces = dict(_PIECES, **{n + "'": [(r, -c) for r, c in _PIECES[n]] for n in _CHIRAL})
+    fixed = True
+
+    def __init__(self, width=9, height=10):
+        super().__init__(width, height)
+
+
+def make_pentomino(width, height, onesided=False):
+    return (OneSidedPentomino if onesided else Pentomino)(width, height)
+
+
 # ------------------------------------------------------------------------ distributed
 class PentominoMapper(Mapper):
     def configure(self, job):
-        self.p = Pentomino(job.get_int("pent.width", 10), job.get_int("pent.height", 6))
+        self.p = make_pentomino(job.get_int("pent.width", 10), job.get_int("pent.height", 6),
+                                job.get_boolean("pent.onesided", False))
 
     def map(self, key, value, output, reporter):
         prefix = [int(t) for t in str(value).split(",") if t]
@@ -210,8 +244,8 @@ class SumReducer(Reducer):
 
 
 def distributed_pentomino(out, width=10, height=6, depth=2, conf=None, cluster=None,
-                          verbose=False):
-    p = Pentomino(width, height)
+                          verbose=False, onesided=False):
+    p = make_pentomino(width, height, onesided)
     prefixes = p.split(depth)
     tmp = tempfile.mkdtemp(prefix="pent-")
     with open(os.path.join(tmp, "prefixes.txt"), "w") as f:
@@ -221,6 +255,7 @@ def distributed_pentomino(out, width=10, height=6, depth=2, conf=None, cluster=N
     job.set_job_name("dancingElephant")
     job.set_int("pent.width", width)
     job.set_int("pent.height", height)
+    job.set_boolean("pent.onesided", bool(onesided))
     job.set_input_format(NLineInputFormat)
     job.set_int("mapred.line.input.format.linespermap", max(1, len(prefixes) // 16))
     job.set_mapper_class(PentominoMapper)
@@ -251,13 +286,37 @@ def main_sudoku(argv=None, cluster=None):
     return 0
 
 
+def run_pentomino(out, width=10, height=6, depth=2, onesided=False, maps=None, conf=None,
+                  cluster=None, gpu=False, verbose=False):
+    """Count the tilings into ``out``; ``gpu``: as the split-level job of
+    hbmr/models/pentomino.py, the classic job if the output is not eligible
+    (the reason is logged).  Returns the count."""
+    if gpu:
+        from ..models import pentomino as P
+        from ._gpu import run_gpu_job
+        rj = run_gpu_job(lambda: P.gpu_job(out, width, height, depth, onesided, maps, base=conf),
+                         "pentomino", conf, cluster, log)
+        if rj is not None:
+            return int(rj._impl.jip.result[0]["solutions"])
+    return distributed_pentomino(out, width, height, depth, conf=conf, cluster=cluster,
+                                 verbose=verbose, onesided=onesided)
+
+
 def main_pentomino(argv=None, cluster=None):
     ap = argparse.ArgumentParser(prog="hbmr pentomino")
     ap.add_argument("output")
-    ap.add_argument("-width", type=int, default=10)
-    ap.add_argument("-height", type=int, default=6)
+    ap.add_argument("-width", type=int, default=None)
+    ap.add_argument("-height", type=int, default=None)
     ap.add_argument("-depth", type=int, default=2)
+    ap.add_argument("-onesided", action="store_true",
+                    help="the 18 one-sided pentominoes (default board 9x10)")
+    ap.add_argument("-m", type=int, default=None, help="maps (with -gpu)")
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a split-level job (exact-cover kernels on GPU slots)")
     a = ap.parse_args(argv)
-    n = distributed_pentomino(a.output, a.width, a.height, a.depth, cluster=cluster, verbose=True)
+    width = a.width if a.width is not None else (9 if a.onesided else 10)
+    height = a.height if a.height is not None else (10 if a.onesided else 6)
+    n = run_pentomino(a.output, width, height, a.depth, a.onesided, a.m, cluster=cluster,
+                      gpu=a.gpu, verbose=True)
     print(f"{n} solutions")
     return 0

@@ -228,6 +228,15 @@ _SIGS = {
     "hbmr_intpair_partition": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p]),
     "hbmr_intpair_lengths": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_intpair_fill": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    # exact cover / Pentomino (native/kernels/exactcover.hip)
+    "hbmr_exactcover_expand_count": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_exactcover_expand_write": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                             c_void_p, c_long, c_void_p, c_long, c_long, c_void_p,
+                                             c_void_p]),
+    "hbmr_exactcover_count_blocks": (c_int, [c_int, c_int, c_int, c_long]),
+    "hbmr_exactcover_count": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                      c_long, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     # PiEstimator (native/kernels/pi.hip)
     "hbmr_pi_halton": (c_int, [ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]),
     # GEMM (native/kernels/gemm.hip)

@@ -333,6 +333,27 @@ int hbmr_intpair_partition(const int64_t* keys, long n, long nparts, int64_t* pa
 int hbmr_intpair_lengths(const int64_t* keys, long n, int32_t* lens, hipStream_t st);
 int hbmr_intpair_fill(const int64_t* keys, const int64_t* offs, long n, uint8_t* dst,
                       hipStream_t st);
+// ---- exact cover (native/kernels/exactcover.hip) -------------------------------
+// Pentomino counting over the placement table of hbmr/ops/exactcover.py: words
+// (1 or 2) 64-bit words per mask, m planar [words][nrows], p = 1 << piece,
+// off[ncells + 1] the buckets by lowest cell.  A state is words + 1 uint64: the
+// occupied cells, then used pieces | prefix index << 32.
+int hbmr_exactcover_expand_count(int words, const uint64_t* m, const uint32_t* p,
+                                 const int32_t* off, int nrows, int ncells,
+                                 const uint64_t* states, long n, int32_t* nchild, hipStream_t st);
+// child_off[n]: exclusive scan of nchild, base: child_off of the first state here
+int hbmr_exactcover_expand_write(int words, const uint64_t* m, const uint32_t* p,
+                                 const int32_t* off, int nrows, int ncells,
+                                 const uint64_t* states, long n, const int64_t* child_off,
+                                 long base, long capacity, uint64_t* out, hipStream_t st);
+// scratch[2]: the work counter (zero it) and the placements made (added to);
+// counts[nprefixes] is added to; wg_clock: null, or [2 * blocks] first start and
+// last end per workgroup on the 100 MHz clock (zero it)
+int hbmr_exactcover_count_blocks(int words, int nrows, int ncells, long n);
+int hbmr_exactcover_count(int words, const uint64_t* m, const uint32_t* p, const int32_t* off,
+                          int nrows, int ncells, const uint64_t* states, long n, long nprefixes,
+                          unsigned long long* scratch, unsigned long long* counts,
+                          unsigned long long* wg_clock, hipStream_t st);
 #endif
 int hbmr_kmeans_padded_k(int k);
 long hbmr_kmeans_accum_workspace_bytes(long n, int k);
@@ -345,6 +366,11 @@ int hbmr_kmeans_map_cpu_f32(const float* X, long n, int d, const float* C, int k
 int hbmr_kmeans_map_cpu_f32_ex(const float* X, long n, int d, const float* C, int k,
                                int32_t* labels, long long* sums, long long* counts, double* cost,
                                int fx_shift, int nthreads, int exact, long* rescored);
+// the exact-cover count of native/kernels/exactcover.hip on the host (same
+// table and states); counts[nprefixes] and *nodes (may be null) are added to
+int hbmr_exactcover_count_cpu(int words, const uint64_t* m, const uint32_t* p, const int32_t* off,
+                              int nrows, int ncells, const uint64_t* states, long n,
+                              long nprefixes, int64_t* counts, uint64_t* nodes, int threads);
 
 #ifdef __cplusplus
 }
