@@ -83,6 +83,20 @@ class UniqValueCount:
         return sorted(self.items)
 
 
+def histogram_report(cs) -> str:
+    """ValueHistogram's report of the counts ``cs`` (ints, ascending): their
+    number, min, median, max, average and standard deviation.  The deviation
+    is a sequential double sum over the sorted counts
+    (ValueHistogram.java:114-120); another summation order gives another last
+    digit, so everything that writes this report calls this function."""
+    if not cs:
+        return "0"
+    n = len(cs)
+    avg = sum(cs) / n
+    sd = (sum((c - avg) ** 2 for c in cs) / n) ** 0.5
+    return f"{n}\t{cs[0]}\t{cs[n // 2]}\t{cs[-1]}\t{avg}\t{sd}"
+
+
 class ValueHistogram:
     """value "v" or "v\\tcount"; report: number of distinct values, then
     min/median/max/average/stddev of the counts (ValueHistogram.java)."""
@@ -96,13 +110,7 @@ class ValueHistogram:
         self.counts[v] = self.counts.get(v, 0) + (int(c) if c else 1)
 
     def getReport(self):  # noqa: N802
-        if not self.counts:
-            return "0"
-        cs = sorted(self.counts.values())
-        n = len(cs)
-        avg = sum(cs) / n
-        sd = (sum((c - avg) ** 2 for c in cs) / n) ** 0.5
-        return f"{n}\t{cs[0]}\t{cs[n // 2]}\t{cs[-1]}\t{avg}\t{sd}"
+        return histogram_report(sorted(self.counts.values()))
 
     def getCombinerOutput(self):  # noqa: N802
         return [f"{v}\t{c}" for v, c in sorted(self.counts.items())]

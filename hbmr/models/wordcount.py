@@ -203,15 +203,37 @@ def make_job(inputs, output, reduces=1, conf=None) -> JobConf:
     return job
 
 
-def main(argv=None):
+def run(inputs, output, reduces=1, conf=None, cluster=None, maps=None, gpu=False):
+    """Run the job; ``gpu``: as the split-level job of hbmr/models/wordtable.py
+    (device reduce, ``reduces`` parts), the classic job if it is not eligible
+    (the reason is logged)."""
+    rj = None
+    if gpu:
+        import logging
+
+        from ..examples._gpu import run_gpu_job
+        from . import wordtable
+        rj = run_gpu_job(lambda: wordtable.wordcount_job(inputs, output, reduces, conf, maps),
+                         "wordcount", conf, cluster, logging.getLogger("hbmr.models.wordcount"))
+    if rj is not None:
+        return rj
+    job = make_job(inputs, output, reduces, conf)
+    if maps:
+        job.set_num_map_tasks(maps)
+    return JobClient.runJob(job, cluster=cluster)
+
+
+def main(argv=None, cluster=None):
     import argparse
     ap = argparse.ArgumentParser(prog="hbmr wordcount")
     ap.add_argument("input", nargs="+")
     ap.add_argument("output")
     ap.add_argument("-r", "--reduces", type=int, default=1)
+    ap.add_argument("-m", "--maps", type=int, default=None)
+    ap.add_argument("-gpu", action="store_true",
+                    help="run as a split-level job (text and word-table kernels on GPU slots)")
     a = ap.parse_args(argv)
-    job = make_job(a.input, a.output, a.reduces)
-    rj = JobClient.runJob(job)
+    rj = run(a.input, a.output, a.reduces, cluster=cluster, maps=a.maps, gpu=a.gpu)
     return 0 if rj.isSuccessful() else 1
 
 

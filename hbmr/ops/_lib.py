@@ -228,6 +228,13 @@ _SIGS = {
     "hbmr_intpair_partition": (c_int, [c_void_p, c_long, c_long, c_void_p, c_void_p]),
     "hbmr_intpair_lengths": (c_int, [c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_intpair_fill": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    # word tables (native/kernels/wordtab.hip)
+    "hbmr_wordtab_tile_bytes": (c_int, []),
+    "hbmr_wordtab_partition": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_uint, c_int,
+                                       c_void_p, c_void_p]),
+    "hbmr_wordtab_lengths": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "hbmr_wordtab_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_long, c_long, c_void_p, c_void_p]),
     # exact cover / Pentomino (native/kernels/exactcover.hip)
     "hbmr_exactcover_expand_count": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                              c_void_p, c_long, c_void_p, c_void_p]),

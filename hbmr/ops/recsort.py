@@ -250,20 +250,34 @@ def _split_point_tensors(split_points, device):
             torch.from_numpy(lens).to(device))
 
 
-def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None):
+def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None, part=None):
     """(perm int32[n], part_records list[nparts]): the record ids ordered by
     (partition, key payload), stable, and the records per partition.
-    ``stats`` (a dict) receives ``rounds``."""
+    ``stats`` (a dict) receives ``rounds``.  ``part`` (int32[n], values in
+    [0, nparts)): the records' partitions, computed by the caller, in place of
+    HashPartitioner's."""
     foff, flen, koff, klen = _rows(index)
     n = int(koff.numel())
     dev = data.device
     if split_points is not None and len(split_points) != nparts - 1:
         raise ValueError(f"{nparts} partitions need {nparts - 1} split points")
+    if part is not None:
+        if split_points is not None:
+            raise ValueError("either split points or precomputed partitions")
+        if part.dtype != torch.int32 or part.numel() != n or part.device != dev:
+            raise ValueError("part: int32[n] on the data's device required")
+        if n and (int(part.min()) < 0 or int(part.max()) >= nparts):
+            raise ValueError("part: a partition outside [0, nparts)")
     if n == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), [0] * nparts
     if n >= 1 << 31:
         raise ValueError("at most 2^31 - 1 records per sort")
     if dev.type != "cuda":
+        if part is not None:
+            keys, parts = payloads(data, index), part.tolist()
+            order = sorted(range(n), key=lambda i: (parts[i], keys[i]))
+            return (torch.tensor(order, dtype=torch.int32),
+                    np.bincount(part.numpy(), minlength=nparts).tolist())
         perm, part_records, _, _ = sort_records_cpu(data, index, nparts, split_points)
         return perm, part_records
     lib = _lib.load()
@@ -275,7 +289,8 @@ def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None):
             raise ValueError("record index points outside the data")
         counts = None
         if split_points is None and nparts > 1:
-            part = hash_partition(data, index, nparts, stream)
+            if part is None:
+                part = hash_partition(data, index, nparts, stream)
             seg64 = part.to(torch.int64)
             perm = torch.arange(n, dtype=torch.int32, device=dev)
             _sort.radix_sort_pairs(seg64, perm, 0, max(1, (nparts - 1).bit_length()), stream)

@@ -333,6 +333,18 @@ int hbmr_intpair_partition(const int64_t* keys, long n, long nparts, int64_t* pa
 int hbmr_intpair_lengths(const int64_t* keys, long n, int32_t* lens, hipStream_t st);
 int hbmr_intpair_fill(const int64_t* keys, const int64_t* offs, long n, uint8_t* dst,
                       hipStream_t st);
+// ---- word tables (native/kernels/wordtab.hip) ----------------------------------
+// The reduce side of the word-count family as hbmr/ops/wordtab.py defines it: a
+// word table is a byte buffer, (start, len) int32 per word and an int64 count per
+// word.  Buffers may have any alignment.
+int hbmr_wordtab_tile_bytes();
+int hbmr_wordtab_partition(const uint8_t* buf, const int32_t* starts, const int32_t* lens, long n,
+                           unsigned seed, int nparts, int32_t* parts, hipStream_t st);
+int hbmr_wordtab_lengths(const int32_t* lens, const int64_t* counts, const int32_t* order, long n,
+                         int32_t* out, hipStream_t st);
+int hbmr_wordtab_fill(const uint8_t* buf, const int32_t* starts, const int32_t* lens,
+                      const int64_t* counts, const int32_t* order, const int64_t* offs, long n,
+                      long total, uint8_t* dst, hipStream_t st);
 // ---- exact cover (native/kernels/exactcover.hip) -------------------------------
 // Pentomino counting over the placement table of hbmr/ops/exactcover.py: words
 // (1 or 2) 64-bit words per mask, m planar [words][nrows], p = 1 << piece,
