@@ -5,7 +5,9 @@ with LongWritable.DecreasingComparator and one reducer).
 
 ``-gpu`` runs the search job as the split-level job of hbmr/models/grep.py
 (DFA regex kernels on the GPU map slots); the sort job is the same.  A pattern
-the GPU matcher does not take logs the reason and runs the classic search."""
+the GPU matcher does not take, or an input it does not read (not a local file,
+or compressed with a codec other than Snappy), logs the reason and runs the
+classic search."""
 from __future__ import annotations
 
 import argparse
@@ -31,7 +33,7 @@ class DecreasingLong:
 
 
 def _search_gpu(inp, out, regex, group, conf, cluster):
-    """The search job as a split job; None if the pattern is not eligible."""
+    """The search job as a split job; None if the pattern or an input is not eligible."""
     from ..models import grep as G
     return run_gpu_job(lambda: G.gpu_job(inp, out, regex, group, base=conf), "search", conf,
                        cluster, log)

@@ -20,7 +20,7 @@ from ..gpu.splitjob import SplitJob
 from ..io.writable import LongWritable, Text
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
 from . import records
-from .wordcount import WordCountSplitJob
+from .wordcount import WordCountSplitJob, compressed_input_reason, count_snappy_decoded
 
 REGEX_KEY = "mapred.mapper.regex"
 GROUP_KEY = "mapred.mapper.regex.group"
@@ -50,6 +50,7 @@ class GrepSplitJob(SplitJob):
     def _input(self, ctx, data):
         from ..mapred import counters as C
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
+        count_snappy_decoded(self, ctx)
 
     def map_gpu(self, ctx, data):
         from ..ops import grep
@@ -99,15 +100,30 @@ class GrepSplitJob(SplitJob):
         return {"distinct": len(items), "matches": sum(n for _, n in items)}
 
 
+def why_input_ineligible(inputs):
+    """None if GPU Grep reads these inputs, else the reason it does not."""
+    import os
+    for f in records.input_files(inputs):
+        if not os.path.isfile(f):
+            return f"input {f} is not a local file"
+        if compressed_input_reason(f) is not None:
+            return compressed_input_reason(f)
+    return None
+
+
 def gpu_job(inputs, output, regex, group=0, base=None, maps=None) -> JobConf:
     """The grep-search job as a split-level job (GPU map slots, CPU slots per
     the hybrid cost model).  Raises ValueError, with the reason, for a pattern
-    the GPU matcher does not take."""
+    the GPU matcher does not take, and for an input that is not a local file or
+    carries the extension of a compression codec other than Snappy."""
     from ..ops import grep
     job = JobConf(base)
     why = grep.why_ineligible(regex, group, job.get_int(grep.MAX_STATES_KEY, grep.MAX_STATES))
     if why is not None:
         raise ValueError(f"pattern {regex!r} is not eligible for the GPU: {why}")
+    why = why_input_ineligible(inputs)
+    if why is not None:
+        raise ValueError(f"grep of {inputs!r} is not eligible for the GPU: {why}")
     job.set_job_name("grep-search-gpu")
     job.set("hbmr.splitjob.class", "hbmr.models.grep:GrepSplitJob")
     job.set(REGEX_KEY, regex)

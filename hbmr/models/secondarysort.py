@@ -26,7 +26,7 @@ from ..gpu.splitjob import SplitJob
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
 from . import records
 from .sort import _owned
-from .wordcount import WordCountSplitJob
+from .wordcount import WordCountSplitJob, compressed_input_reason, count_snappy_decoded
 
 SECONDARYSORT_GROUP = "hbmr.SecondarySortCounters"
 SECONDARYSORT_CPU_FALLBACK_SPLITS = "SECONDARYSORT_CPU_FALLBACK_SPLITS"
@@ -52,6 +52,7 @@ class SecondarySortSplitJob(SplitJob):
         from ..mapred import counters as C
         from ..ops import intpair
         stream = getattr(ctx, "stream", None)
+        count_snappy_decoded(self, ctx)
         parsed = intpair.parse(data, stream)
         keys = parsed.keys
         if parsed.irregular:
@@ -119,7 +120,6 @@ class SecondarySortSplitJob(SplitJob):
 
 def why_ineligible(inputs, base=None):
     """None if GPU SecondarySort takes this job, else the reason it does not."""
-    from ..io.compress import codec_for_path
     if base is not None and base.get_boolean("mapred.output.compress", False):
         return "compressed output"
     if base is not None and base.get(SEPARATOR_KEY, "\t") != "\t":
@@ -127,16 +127,16 @@ def why_ineligible(inputs, base=None):
     for f in records.input_files(inputs):
         if not os.path.isfile(f):
             return f"input {f} is not a local file"
-        if codec_for_path(f) is not None:
-            return f"compressed input {f}"
+        if compressed_input_reason(f) is not None:
+            return compressed_input_reason(f)
     return None
 
 
 def gpu_job(inputs, output, reduces=1, base=None, maps=None) -> JobConf:
     """SecondarySort as a split-level job (GPU map slots, CPU slots per the
     hybrid cost model).  Raises ValueError, with the reason, for anything not
-    eligible: an input that is not a local file or carries a compression
-    codec's extension, compressed output, an output separator other than tab."""
+    eligible: an input that is not a local file or carries the extension of
+    a compression codec other than Snappy, compressed output, an output separator other than tab."""
     why = why_ineligible(inputs, base)
     if why is not None:
         raise ValueError(f"secondarysort of {inputs!r} is not eligible for the GPU: {why}")

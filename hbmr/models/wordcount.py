@@ -245,7 +245,9 @@ def main(argv=None, cluster=None):
 # shuffle is one all-to-all-v of "word\n" bytes + one of counts (RCCL over
 # xGMI), and each tracker writes its partition sorted by Text key order, in
 # TextOutputFormat's "word\tcount" lines — the classic job's output, byte for
-# byte.
+# byte.  A `.snappy` file is one whole split: it is decoded on the device
+# (hbmr/ops/snappydec.py) and the decoded text is what stays resident.  The
+# loader is shared by GPU Grep, GPU SecondarySort and the word-table jobs.
 from ..gpu.splitjob import SplitJob, SplitSpec  # noqa: E402
 
 
@@ -286,6 +288,44 @@ def read_text_split(path, start, length, chunk=1 << 16) -> bytes:
         return body + b"".join(tail)
 
 
+COMPRESSED_INPUT_GROUP = "hbmr.CompressedInputCounters"
+SNAPPY_DECODED_BYTES = "SNAPPY_DECODED_BYTES"
+
+
+def is_snappy(path) -> bool:
+    """Whether ``path`` carries SnappyCodec's extension: the one codec whose
+    files the split-level text jobs take (decoded by hbmr/ops/snappydec.py)."""
+    from ..io.compress import SnappyCodec, codec_for_path
+    return isinstance(codec_for_path(path), SnappyCodec)
+
+
+def compressed_input_reason(path):
+    """``compressed input <path>`` for a file of any codec but Snappy, else None."""
+    from ..io.compress import codec_for_path
+    if codec_for_path(path) is not None and not is_snappy(path):
+        return f"compressed input {path}"
+    return None
+
+
+def load_text_file(job, key, path, device):
+    """The decoded bytes of the ``.snappy`` file ``path`` on ``device``.  The
+    split ``key`` of ``job`` is noted as decoded here, for the map's counter."""
+    from ..ops import snappydec
+    t = snappydec.decode_file(path, device)
+    notes = job.__dict__.setdefault("_snappy_decoded", {})
+    notes[key] = notes.get(key, 0) + int(t.numel())
+    return t
+
+
+def count_snappy_decoded(job, ctx):
+    """SNAPPY_DECODED_BYTES of a map: what its own load decoded, on the device
+    or in the twin — nothing for a split found resident."""
+    key = (getattr(ctx.spec, "split", None) or {}).get("key")
+    n = job.__dict__.get("_snappy_decoded", {}).pop(key, 0)
+    if n:
+        ctx.reporter.incrCounter(COMPRESSED_INPUT_GROUP, SNAPPY_DECODED_BYTES, n)
+
+
 class WordCountSplitJob(SplitJob):
     collective_reduce = True
     needs_reduce = True
@@ -309,6 +349,10 @@ class WordCountSplitJob(SplitJob):
     def load_split(self, spec: SplitSpec, device):
         import torch
         p = spec.params
+        if is_snappy(p["path"]):
+            # a compressed file is one whole split (TextInputFormat.is_splitable):
+            # no first-line skip; what stays resident under the key is the text
+            return load_text_file(self, spec.key, p["path"], device)
         data = read_text_split(p["path"], p["start"], p["length"])
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8) if data else \
             torch.empty(0, dtype=torch.uint8)
@@ -318,6 +362,7 @@ class WordCountSplitJob(SplitJob):
         from ..mapred import counters as C
         from ..ops import text
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
+        count_snappy_decoded(self, ctx)
         return text.count_words(data, getattr(ctx, "stream", None))
 
     def map_gpu(self, ctx, data):

@@ -36,7 +36,8 @@ from ..io.writable import hash_bytes
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
 from . import records
 from .sort import owner_of
-from .wordcount import WordCountSplitJob
+from .wordcount import (WordCountSplitJob, compressed_input_reason, count_snappy_decoded,
+                        is_snappy, load_text_file)
 
 PROGRAM_KEY = "hbmr.wordtable.program"
 WORDTABLE_GROUP = "hbmr.WordTableCounters"
@@ -114,10 +115,40 @@ class WordTableSplitJob(SplitJob):
         if "paths" not in spec.params:
             return WordCountSplitJob.load_split(self, spec, device)
         import torch
-        data = read_files(spec.params["paths"])
+        paths = spec.params["paths"]
+        if any(is_snappy(p) for p in paths):
+            return self._load_files_decoded(spec, device)
+        data = read_files(paths)
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8) if data else \
             torch.empty(0, dtype=torch.uint8)
         return t if str(device) == "cpu" else t.to(device)
+
+    def _load_files_decoded(self, spec, device):
+        """:func:`read_files` where some files are ``.snappy``: those are decoded
+        on ``device``, the plain ones copied there, and the join rule is the
+        same — a newline after any file that lacks one (one host read of the
+        files' last bytes for the split)."""
+        import torch
+        dev = torch.device(device)
+        pieces = []
+        for p in spec.params["paths"]:
+            if is_snappy(p):
+                t = load_text_file(self, spec.key, p, device)
+            else:
+                raw = read_files([p])
+                t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev) if raw else None
+            if t is not None and t.numel():
+                pieces.append(t)
+        if not pieces:
+            return torch.empty(0, dtype=torch.uint8, device=dev)
+        last = torch.stack([t[-1] for t in pieces]).tolist()
+        newline = torch.tensor([10], dtype=torch.uint8, device=dev)
+        out = []
+        for t, b in zip(pieces, last):
+            out.append(t)
+            if b != 10:
+                out.append(newline)
+        return torch.cat(out) if len(out) > 1 else out[0]
 
     # -- map --------------------------------------------------------------------------
     def _map(self, ctx, data):
@@ -126,6 +157,7 @@ class WordTableSplitJob(SplitJob):
         from ..mapred import counters as C
         from ..ops import text, wordtab
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
+        count_snappy_decoded(self, ctx)
         if self.decoded and wordtab.flag_nonclassic(data):
             ctx.reporter.incrCounter(WORDTABLE_GROUP, WORDTABLE_CPU_FALLBACK_SPLITS, 1)
             blob, counts = text._table_from(classic_words(bytes(data.cpu().numpy())))
@@ -263,7 +295,6 @@ def pack_words(buf, starts, lens, order):
 # ----------------------------------------------------------------------------- builders
 def why_ineligible(inputs, reduces, base=None):
     """None if the word-table job takes this job, else the reason it does not."""
-    from ..io.compress import codec_for_path
     if reduces < 1:
         return f"{reduces} reduces: the map output itself is the job's output"
     if base is not None and base.get_boolean("mapred.output.compress", False):
@@ -273,8 +304,8 @@ def why_ineligible(inputs, reduces, base=None):
     for f in records.input_files(inputs):
         if not os.path.isfile(f):
             return f"input {f} is not a local file"
-        if codec_for_path(f) is not None:
-            return f"compressed input {f}"
+        if compressed_input_reason(f) is not None:
+            return compressed_input_reason(f)
     return None
 
 
@@ -282,7 +313,7 @@ def gpu_job(program, inputs, output, reduces=1, base=None, maps=None) -> JobConf
     """``program`` (a key of PROGRAMS) as a split-level job (GPU map slots, CPU
     slots per the hybrid cost model).  Raises ValueError, with the reason, for
     anything not eligible: no reduces, an input that is not a local file or
-    carries a compression codec's extension, compressed output, an output
+    carries the extension of a compression codec other than Snappy, compressed output, an output
     separator other than tab."""
     if program not in PROGRAMS:
         raise KeyError(program)

@@ -235,6 +235,8 @@ _SIGS = {
     "hbmr_wordtab_lengths": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
     "hbmr_wordtab_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_long, c_long, c_void_p, c_void_p]),
+    # Snappy decode (native/kernels/snappydec.hip)
+    "hbmr_snappy_decode": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     # exact cover / Pentomino (native/kernels/exactcover.hip)
     "hbmr_exactcover_expand_count": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                              c_void_p, c_long, c_void_p, c_void_p]),
