@@ -18,6 +18,7 @@ import re
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import FileOutputFormat, JobConf
 from . import records
+from .wordcount import count_snappy_decoded
 
 OP_KEY = "hbmr.join.op"
 OUT_KEY_CLASS_KEY = "hbmr.join.output.key.class"
@@ -58,7 +59,8 @@ class JoinSplitJob(SplitJob):
     def load_split(self, spec: SplitSpec, device):
         sources, vclasses = [], []
         for f in spec.params["files"]:
-            sources.append(records.load_record_split(f["path"], f["start"], f["length"], device))
+            sources.append(records.load_job_split(self, spec.key, f["path"], f["start"],
+                                                  f["length"], device))
             vclasses.append(records.first_classes([f["path"]])[1])
         return {"sources": sources, "value_classes": vclasses, "part": spec.params["part"],
                 "files": [f["path"] for f in spec.params["files"]]}
@@ -83,6 +85,7 @@ class JoinSplitJob(SplitJob):
                                  sum(int(i.shape[1]) for _, i in sources))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES,
                                  sum(int(d.numel()) for d, _ in sources))
+        count_snappy_decoded(self, ctx)
         headers = None
         if self.op != "override":
             headers = recjoin.tuple_headers([class_for_java_name(v)

@@ -25,14 +25,15 @@ def input_files(inputs):
 
 def file_reason(f, seen=None):
     """None if the record kernels take the SequenceFile ``f`` (a local file,
-    uncompressed, byte-string keys), else the reason they do not.  ``seen`` (a
-    set) receives the (key class, value class) names of a file they take."""
+    uncompressed or RECORD- / BLOCK-compressed with SnappyCodec, byte-string
+    keys), else the reason they do not.  ``seen`` (a set) receives the (key
+    class, value class) names of a file they take."""
     from ..io import sequencefile as seqf
-    from ..ops import recsort
+    from ..ops import recsort, seqz
     if not os.path.isfile(f):
         return f"input {f} is not a local file"
     with seqf.Reader(f) as r:
-        if r.compression != seqf.NONE:
+        if r.compression != seqf.NONE and not seqz.is_snappy_file(r):
             return f"{r.compression}-compressed input {f}"
         if r.key_class_name not in recsort.KEY_CLASSES:
             return (f"key class {r.key_class_name} of {f} (byte-string keys only: "
@@ -51,16 +52,47 @@ def first_classes(files):
         return r.key_class_name, r.value_class_name
 
 
-def load_record_split(path, start, length, device):
-    """(data uint8[bytes], index int64[4, n]) of ``recsort.index_records`` as
-    tensors on ``device``."""
+def is_snappy_compressed(path) -> bool:
+    """Whether the SequenceFile ``path`` is RECORD- or BLOCK-compressed with
+    SnappyCodec: the compressed files :func:`load_record_split` takes."""
+    from ..ops import seqz
+    return seqz.file_header(path) is not None
+
+
+def _load(path, start, length, device):
+    """(data, index, compressed): the split, and whether it was decompressed.
+    The file's header is looked at once, here."""
     import torch
 
-    from ..ops import recsort
+    from ..ops import recsort, seqz
+    header = seqz.file_header(path)
+    if header is not None:
+        return (*seqz.load_split(path, start, length, device, header=header), True)
     data, index = recsort.index_records(path, start, length)
     data, index = torch.from_numpy(data), torch.from_numpy(index)
     if str(device) != "cpu":
         data, index = data.to(device), index.to(device)
+    return data, index, False
+
+
+def load_record_split(path, start, length, device):
+    """(data uint8[bytes], index int64[4, n]) of the records a
+    SequenceFileRecordReader over (path, start, length) returns, as tensors on
+    ``device``: of an uncompressed file the raw range and index of
+    ``recsort.index_records``; of a Snappy RECORD- or BLOCK-compressed file the
+    frames of the decompressed records back to back, decoded and assembled on
+    the device (``hbmr.ops.seqz.load_split``)."""
+    return _load(path, start, length, device)[:2]
+
+
+def load_job_split(job, key, path, start, length, device):
+    """:func:`load_record_split` for the split ``key`` of ``job``; the bytes a
+    compressed file decoded to are noted for the map's SNAPPY_DECODED_BYTES
+    (``wordcount.count_snappy_decoded``: nothing for a split found resident)."""
+    data, index, compressed = _load(path, start, length, device)
+    if compressed:
+        notes = job.__dict__.setdefault("_snappy_decoded", {})
+        notes[key] = notes.get(key, 0) + int(data.numel())
     return data, index
 
 

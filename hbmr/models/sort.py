@@ -2,9 +2,11 @@
 split-level job.
 
 The classic job runs IdentityMapper/IdentityReducer through the generic sort
-buffer, record by record.  Here a split of an uncompressed
-``SequenceFile<BytesWritable|Text, *>`` is indexed in one native pass
-(native/io/recindex.cc) and lies in HBM as raw bytes + index; the map
+buffer, record by record.  Here a split of a
+``SequenceFile<BytesWritable|Text, *>`` lies in HBM as bytes + index: an
+uncompressed one is indexed in one native pass (native/io/recindex.cc), a
+Snappy RECORD- or BLOCK-compressed one is decoded and assembled into the same
+frames on the device (hbmr/ops/seqz.py); the map
 partitions (HashPartitioner over the key payload, or TotalOrderPartitioner's
 split points), sorts by (partition, key bytes) and gathers the frames into one
 blob per split (native/kernels/recsort.hip).  Partition ``p`` of
@@ -22,6 +24,7 @@ from __future__ import annotations
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import FileInputFormat, FileOutputFormat, JobConf
 from . import records
+from .wordcount import count_snappy_decoded
 
 KEY_CLASS_KEY = "hbmr.sort.key.class"
 VALUE_CLASS_KEY = "hbmr.sort.value.class"
@@ -85,7 +88,8 @@ class SortSplitJob(SplitJob):
 
     def load_split(self, spec: SplitSpec, device):
         p = spec.params
-        data, index = records.load_record_split(p["path"], p["start"], p["length"], device)
+        data, index = records.load_job_split(self, spec.key, p["path"], p["start"], p["length"],
+                                             device)
         return {"data": data, "index": index}
 
     def load_split_sample(self, spec, device, fraction):
@@ -106,6 +110,7 @@ class SortSplitJob(SplitJob):
         n = int(index.shape[1])
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, n)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
+        count_snappy_decoded(self, ctx)
         perm, nrec, nbytes, blob = recsort.sort_records(
             data, index, self.nparts, self.split_points, getattr(ctx, "stream", None))
         meta = _meta(index)[perm.to(index.device).long()]
@@ -208,7 +213,8 @@ def gpu_job(inputs, output, reduces=1, partition_file=None, base=None, maps=None
     """Sort as a split-level job (GPU map slots, CPU slots per the hybrid cost
     model).  ``partition_file``: a TotalOrderPartitioner partition file whose
     keys become the split points.  Raises ValueError, with the reason, for
-    anything not eligible: RECORD- or BLOCK-compressed input, a key class other
+    anything not eligible: RECORD- or BLOCK-compressed input of a codec other
+    than SnappyCodec, a key class other
     than BytesWritable or Text, a custom input/output format or comparator."""
     why = why_ineligible(inputs, base, in_format, out_format)
     if why is not None:

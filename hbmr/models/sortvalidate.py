@@ -22,6 +22,7 @@ from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import FileInputFormat, JobConf
 from . import records
 from .sort import SortSplitJob
+from .wordcount import count_snappy_decoded
 
 GROUP = "SortValidator"
 SORTED_DIR_KEY = "sortvalidate.sorted.dir"
@@ -77,6 +78,7 @@ class ValidateSplitJob(SplitJob):
         rep = ctx.reporter
         rep.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, n)
         rep.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
+        count_snappy_decoded(self, ctx)
         rep.incrCounter(GROUP, f"{side}_RECORDS", n)
         rep.incrCounter(GROUP, f"{side}_BYTES", nbytes)
         rep.incrCounter(GROUP, f"{side}_HASH_SUM", hs)
@@ -132,12 +134,14 @@ def gpu_job(sort_input, sort_output, total_order=False, base=None) -> JobConf:
 
 def range_overlaps(sort_output, outs):
     """The adjacent non-empty parts (``outs``, in order) whose key ranges overlap:
-    the first and last key payload of each from the native record index."""
+    the first and last key payload of each from the native record index, of a
+    compressed part from the split loader's."""
     from ..ops import recsort
     bounds = []
     for p in outs:
         path = os.path.join(sort_output, p)
-        data, index = recsort.index_records(path, 0, os.path.getsize(path))
+        data, index = (t.numpy() for t in records.load_record_split(
+            path, 0, os.path.getsize(path), "cpu"))
         if index.shape[1]:
             koff, klen = index[recsort.KOFF], index[recsort.KLEN]
             bounds.append(tuple(data[koff[i]:koff[i] + klen[i]].tobytes() for i in (0, -1)))

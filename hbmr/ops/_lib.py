@@ -237,6 +237,16 @@ _SIGS = {
                                   c_long, c_long, c_void_p, c_void_p]),
     # Snappy decode (native/kernels/snappydec.hip)
     "hbmr_snappy_decode": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    # compressed SequenceFile splits (native/kernels/seqblock.hip)
+    "hbmr_seqblock_vint": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "hbmr_seqblock_index": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p]),
+    "hbmr_seqblock_assemble": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_long,
+                                       c_void_p]),
+    "hbmr_seqblock_heads": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_long, c_void_p, c_long, c_void_p]),
     # exact cover / Pentomino (native/kernels/exactcover.hip)
     "hbmr_exactcover_expand_count": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                              c_void_p, c_long, c_void_p, c_void_p]),
