@@ -88,6 +88,7 @@ def estimate(maps, samples, conf=None, cluster=None, verbose=False):
 
 
 from ..gpu.splitjob import SplitJob, SplitSpec  # noqa: E402
+from ..models.splits import place  # noqa: E402
 
 
 class PiSplitJob(SplitJob):
@@ -102,7 +103,7 @@ class PiSplitJob(SplitJob):
     def get_splits(self, conf, trackers):
         out = []
         for i in range(self.maps):
-            loc = [trackers[i * len(trackers) // self.maps]] if trackers else []
+            loc = place(i, self.maps, trackers)
             out.append(SplitSpec(i, f"pi:{i}:{self.samples}", "range",
                                  {"offset": i * self.samples, "size": self.samples}, loc, 0))
         return out

@@ -24,6 +24,7 @@ from ..io.writable import IntWritable, NullWritable
 from ..mapred.api import InputFormat, InputSplit, Mapper, Partitioner, RecordReader, Reducer
 from ..mapred.formats import NullOutputFormat
 from ..mapred.jobconf import JobConf
+from ..models.splits import place
 
 
 # --------------------------------------------------------------------------- classic
@@ -134,7 +135,7 @@ class SplitSleepJob(SplitJob):
     def get_splits(self, conf, trackers):
         out = []
         for i in range(self.maps):
-            loc = [trackers[i * len(trackers) // self.maps]] if trackers else []
+            loc = place(i, self.maps, trackers)
             out.append(SplitSpec(i, f"sleep:{i}", "range", {"i": i}, loc, 0))
         return out
 

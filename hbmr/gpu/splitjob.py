@@ -20,6 +20,8 @@ Subclasses implement:
 * ``combine(ctx, outputs)``        -> one combined output on this tracker
 * ``reduce(ctx, combined)``        -> result (collectives via ctx.comm)
 * ``job_succeeded(jip)``           -> optional hook on the JobTracker
+
+A new job over files starts from the mixins and helpers of ``hbmr/models/splits.py``.
 """
 from __future__ import annotations
 

@@ -18,9 +18,8 @@ from __future__ import annotations
 
 from ..gpu.splitjob import SplitJob
 from ..io.writable import LongWritable, Text
-from ..mapred import FileInputFormat, FileOutputFormat, JobConf
-from . import records
-from .wordcount import WordCountSplitJob, compressed_input_reason, count_snappy_decoded
+from ..mapred import JobConf
+from . import records, splits
 
 REGEX_KEY = "mapred.mapper.regex"
 GROUP_KEY = "mapred.mapper.regex.group"
@@ -28,14 +27,9 @@ GREP_GROUP = "hbmr.GrepCounters"
 GREP_CPU_FALLBACK_SPLITS = "GREP_CPU_FALLBACK_SPLITS"
 
 
-class GrepSplitJob(SplitJob):
+class GrepSplitJob(splits.FinishesOutput, splits.TextSplits, SplitJob):
     collective_reduce = True
     needs_reduce = True
-
-    get_splits = WordCountSplitJob.get_splits
-    load_split = WordCountSplitJob.load_split
-    _shuffle = staticmethod(WordCountSplitJob._shuffle)
-    job_succeeded = WordCountSplitJob.job_succeeded
 
     def configure(self, conf):
         from ..ops import grep
@@ -50,7 +44,7 @@ class GrepSplitJob(SplitJob):
     def _input(self, ctx, data):
         from ..mapred import counters as C
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
 
     def map_gpu(self, ctx, data):
         from ..ops import grep
@@ -75,20 +69,15 @@ class GrepSplitJob(SplitJob):
         return grep.count_matches_cpu(raw, self.regex, self.group)
 
     def combine(self, ctx, outputs):
-        import torch
         from ..ops import grep
-        dev = ctx.device if ctx.device is not None else torch.device("cpu")
-        blobs = [b.to(dev) for b, _ in outputs]
-        counts = [c.to(dev) for _, c in outputs]
-        blob = torch.cat(blobs) if blobs else torch.empty(0, dtype=torch.uint8, device=dev)
-        cnt = torch.cat(counts) if counts else torch.empty(0, dtype=torch.int64, device=dev)
+        blob, cnt = splits.cat_tables(outputs, splits.device_of(ctx))
         return grep.merge_tables(blob, cnt, max(1, ctx.world_size))
 
     def reduce(self, ctx, combined):
         from ..mapred import counters as C
         from ..ops import grep, text
         blob, counts, part_bytes, part_words = combined
-        rblob, rcounts = self._shuffle(ctx, blob, counts, part_bytes, part_words)
+        rblob, rcounts = splits.shuffle_tables(ctx, blob, counts, part_bytes, part_words)
         mblob, mcounts, _, _ = grep.merge_tables(rblob, rcounts, 1)
         items = text.sorted_items(mblob, mcounts)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_GROUPS, len(items))
@@ -100,36 +89,21 @@ class GrepSplitJob(SplitJob):
         return {"distinct": len(items), "matches": sum(n for _, n in items)}
 
 
-def why_input_ineligible(inputs):
-    """None if GPU Grep reads these inputs, else the reason it does not."""
-    import os
-    for f in records.input_files(inputs):
-        if not os.path.isfile(f):
-            return f"input {f} is not a local file"
-        if compressed_input_reason(f) is not None:
-            return compressed_input_reason(f)
-    return None
-
-
 def gpu_job(inputs, output, regex, group=0, base=None, maps=None) -> JobConf:
     """The grep-search job as a split-level job (GPU map slots, CPU slots per
     the hybrid cost model).  Raises ValueError, with the reason, for a pattern
     the GPU matcher does not take, and for an input that is not a local file or
     carries the extension of a compression codec other than Snappy."""
     from ..ops import grep
-    job = JobConf(base)
-    why = grep.why_ineligible(regex, group, job.get_int(grep.MAX_STATES_KEY, grep.MAX_STATES))
+    why = grep.why_ineligible(regex, group,
+                              JobConf(base).get_int(grep.MAX_STATES_KEY, grep.MAX_STATES))
     if why is not None:
         raise ValueError(f"pattern {regex!r} is not eligible for the GPU: {why}")
-    why = why_input_ineligible(inputs)
+    why = splits.text_input_reason(inputs)
     if why is not None:
         raise ValueError(f"grep of {inputs!r} is not eligible for the GPU: {why}")
-    job.set_job_name("grep-search-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.grep:GrepSplitJob")
+    job = splits.file_job(base, "grep-search-gpu", "hbmr.models.grep:GrepSplitJob", inputs,
+                          output, maps)
     job.set(REGEX_KEY, regex)
     job.set_int(GROUP_KEY, group)
-    FileInputFormat.setInputPaths(job, *([inputs] if isinstance(inputs, str) else inputs))
-    FileOutputFormat.setOutputPath(job, output)
-    if maps:
-        job.set_num_map_tasks(maps)
     return job

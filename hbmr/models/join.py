@@ -16,9 +16,8 @@ import os
 import re
 
 from ..gpu.splitjob import SplitJob, SplitSpec
-from ..mapred import FileOutputFormat, JobConf
-from . import records
-from .wordcount import count_snappy_decoded
+from ..mapred import JobConf
+from . import records, splits
 
 OP_KEY = "hbmr.join.op"
 OUT_KEY_CLASS_KEY = "hbmr.join.output.key.class"
@@ -26,7 +25,7 @@ OUT_VALUE_CLASS_KEY = "hbmr.join.output.value.class"
 JOB_NAME = "join-gpu"
 
 
-class JoinSplitJob(SplitJob):
+class JoinSplitJob(splits.BothSlots, splits.FinishesOutput, SplitJob):
     collective_reduce = True
     needs_reduce = False
 
@@ -46,20 +45,20 @@ class JoinSplitJob(SplitJob):
         """One split per partition: the i-th file of every source, in the order
         CompositeInputFormat.getSplits gives them."""
         from ..mapred.join import CompositeInputFormat
-        splits = CompositeInputFormat().getSplits(JobConf(conf), 1)
+        found = CompositeInputFormat().getSplits(JobConf(conf), 1)
         out = []
-        for i, cs in enumerate(splits):
+        for i, cs in enumerate(found):
             files = [{"path": s.path, "start": s.start, "length": s.length} for s in cs.splits]
             key = "join:" + "|".join(f"{f['path']}:{f['start']}:{f['length']}" for f in files)
-            loc = [trackers[i * len(trackers) // len(splits)]] if trackers else []
-            out.append(SplitSpec(i, key, "file", {"files": files, "part": i}, loc,
+            out.append(SplitSpec(i, key, "file", {"files": files, "part": i},
+                                 splits.place(i, len(found), trackers),
                                  sum(f["length"] for f in files)))
         return out
 
     def load_split(self, spec: SplitSpec, device):
         sources, vclasses = [], []
         for f in spec.params["files"]:
-            sources.append(records.load_job_split(self, spec.key, f["path"], f["start"],
+            sources.append(splits.load_job_split(self, spec.key, f["path"], f["start"],
                                                   f["length"], device))
             vclasses.append(records.first_classes([f["path"]])[1])
         return {"sources": sources, "value_classes": vclasses, "part": spec.params["part"],
@@ -85,7 +84,7 @@ class JoinSplitJob(SplitJob):
                                  sum(int(i.shape[1]) for _, i in sources))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES,
                                  sum(int(d.numel()) for d, _ in sources))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         headers = None
         if self.op != "override":
             headers = recjoin.tuple_headers([class_for_java_name(v)
@@ -105,16 +104,10 @@ class JoinSplitJob(SplitJob):
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_OUTPUT_RECORDS, n)
         return {"records": n}
 
-    def map_gpu(self, ctx, split):
-        return self._map(ctx, split)
-
-    def map_cpu(self, ctx, split):
-        return self._map(ctx, split)
-
     def job_succeeded(self, jip):
         if self.out:
             os.makedirs(self.out, exist_ok=True)
-            records.finish_output(self.out)
+        super().job_succeeded(jip)
 
 
 def _flat_sources(expr, base):
@@ -201,13 +194,10 @@ def gpu_job(inputs, output, join_type="inner", reduces=0, base=None, in_format=N
     kc, vc = records.first_classes([f for p in paths for f in records.input_files(p)])
     if op != "override":
         vc = TupleWritable.JAVA_NAME
-    job = JobConf(base)
-    job.set_job_name(JOB_NAME)
-    job.set("hbmr.splitjob.class", "hbmr.models.join:JoinSplitJob")
+    job = splits.file_job(base, JOB_NAME, "hbmr.models.join:JoinSplitJob", output=output)
     job.set("mapred.join.expr", expr)
     job.set(OP_KEY, op)
     job.set(OUT_KEY_CLASS_KEY, class_name(out_key) if out_key is not None else kc)
     job.set(OUT_VALUE_CLASS_KEY, class_name(out_value) if out_value is not None else vc)
     job.set_num_reduce_tasks(0)
-    FileOutputFormat.setOutputPath(job, output)
     return job

@@ -22,6 +22,7 @@ import torch
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..mapred import counters as C
 from ..ops import gemm as G
+from .splits import place
 
 M_KEY, K_KEY, N_KEY = "hbmr.matmul.m", "hbmr.matmul.k", "hbmr.matmul.n"
 ROWS_KEY = "hbmr.matmul.split.rows"
@@ -108,7 +109,7 @@ class MatmulSplitJob(SplitJob):
         for i in range(nsplit):
             r0 = i * self.rows
             r = min(self.rows, self.m - r0)
-            loc = [trackers[i * len(trackers) // nsplit]] if trackers else []
+            loc = place(i, nsplit, trackers)
             out.append(SplitSpec(i, f"mm:{self.seed}:{self.k}:{r0}:{r}", "range",
                                  {"row0": r0, "rows": r}, loc, r * self.k * 2))
         return out

@@ -14,8 +14,8 @@ from __future__ import annotations
 import functools
 
 from ..gpu.splitjob import SplitJob, SplitSpec
-from ..mapred import FileOutputFormat, JobConf
-from . import records
+from ..mapred import JobConf
+from . import records, splits
 
 WIDTH_KEY, HEIGHT_KEY, DEPTH_KEY = "pent.width", "pent.height", "pent.depth"
 ONESIDED_KEY = "pent.onesided"
@@ -38,7 +38,7 @@ def classic_maps(nprefixes):
     return max(1, -(-nprefixes // per))
 
 
-class PentominoSplitJob(SplitJob):
+class PentominoSplitJob(splits.FinishesOutput, SplitJob):
     collective_reduce = True
     needs_reduce = True
     cache_inputs = False           # a split is its own spec: nothing to keep
@@ -59,9 +59,8 @@ class PentominoSplitJob(SplitJob):
         out = []
         for i in range(maps):
             lo, hi = i * n // maps, (i + 1) * n // maps
-            loc = [trackers[i * len(trackers) // maps]] if trackers else []
             out.append(SplitSpec(i, f"pentomino:{self.shape}:{lo}:{hi}", "range",
-                                 {"lo": lo, "hi": hi}, loc, 0))
+                                 {"lo": lo, "hi": hi}, splits.place(i, maps, trackers), 0))
         return out
 
     def load_split(self, spec, device):
@@ -106,18 +105,10 @@ class PentominoSplitJob(SplitJob):
                     f.write(b"solutions\t%d\n" % total)
         return {"solutions": total}
 
-    def job_succeeded(self, jip):
-        if self.out:
-            records.finish_output(self.out)
-
 
 def why_ineligible(out, base=None):
     """None if GPU Pentomino takes this job, else the reason it does not."""
-    if base is not None and base.get_boolean("mapred.output.compress", False):
-        return "compressed output"
-    if "://" in str(out) and not str(out).startswith("file://"):
-        return f"output directory {out} is not a local one"
-    return None
+    return splits.local_output_reason(out, base)
 
 
 def gpu_job(out, width=10, height=6, depth=2, onesided=False, maps=None, base=None) -> JobConf:
@@ -133,14 +124,12 @@ def gpu_job(out, width=10, height=6, depth=2, onesided=False, maps=None, base=No
         _, prefixes = problem(width, height, depth, bool(onesided))
     except ValueError as e:
         raise ValueError(f"pentomino {width}x{height} is not eligible for the GPU: {e}") from e
-    job = JobConf(base)
-    job.set_job_name("dancingElephant-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.pentomino:PentominoSplitJob")
+    job = splits.file_job(base, "dancingElephant-gpu", "hbmr.models.pentomino:PentominoSplitJob",
+                          output=strip_scheme(str(out)),
+                          maps=max(1, maps or classic_maps(len(prefixes))))
     job.set_int(WIDTH_KEY, width)
     job.set_int(HEIGHT_KEY, height)
     job.set_int(DEPTH_KEY, depth)
     job.set_boolean(ONESIDED_KEY, bool(onesided))
-    job.set_num_map_tasks(max(1, maps or classic_maps(len(prefixes))))
     job.set_num_reduce_tasks(1)
-    FileOutputFormat.setOutputPath(job, strip_scheme(str(out)))
     return job

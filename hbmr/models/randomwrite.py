@@ -24,8 +24,8 @@ import os
 import struct
 
 from ..gpu.splitjob import SplitJob, SplitSpec
-from ..mapred import FileOutputFormat, JobConf
-from . import records
+from ..mapred import JobConf
+from . import records, splits
 
 SEED_KEY = "hbmr.randomwrite.seed"
 RESIDENT_KEY = "hbmr.randomwrite.gpu.resident"
@@ -56,13 +56,7 @@ def vocabulary():
     return randomwriter._WORDS
 
 
-def cache_key(path, size):
-    """The split-cache key of the whole file ``path`` of ``size`` bytes: GPU
-    Sort's and GPU SortValidator's for a file they take as one split."""
-    return f"sort:{path}:0:{size}"
-
-
-class RandomWriteSplitJob(SplitJob):
+class RandomWriteSplitJob(splits.BothSlots, splits.FinishesOutput, SplitJob):
     collective_reduce = True
     needs_reduce = False
     cache_inputs = False           # a split is its own spec: nothing to keep
@@ -85,12 +79,9 @@ class RandomWriteSplitJob(SplitJob):
     # -- input ------------------------------------------------------------------------
     def get_splits(self, conf, trackers):
         maps = max(1, conf.get_num_map_tasks())
-        out = []
-        for i in range(maps):
-            loc = [trackers[i * len(trackers) // maps]] if trackers else []
-            out.append(SplitSpec(i, f"randomwrite:{self.out}:{self.seed}:{i}", "synthetic",
-                                 {"map": i}, loc, max(0, self.total)))
-        return out
+        return [SplitSpec(i, f"randomwrite:{self.out}:{self.seed}:{i}", "synthetic", {"map": i},
+                          splits.place(i, maps, trackers), max(0, self.total))
+                for i in range(maps)]
 
     def load_split(self, spec, device):
         return spec
@@ -148,34 +139,21 @@ class RandomWriteSplitJob(SplitJob):
             return
         data, index = kept
         where = dev.index if isinstance(dev, torch.device) and dev.type == "cuda" else "cpu"
-        key = cache_key(os.path.join(strip_scheme(self.out), name), size)
+        key = splits.whole_file_key(os.path.join(strip_scheme(self.out), name), size)
         split = {"data": data, "index": index}
         try:
             cache.put(key, where, split, int(data.numel() + index.numel() * 8))
         except Exception:  # noqa: BLE001  (a cache that turns the entry away: the file stands)
             pass
 
-    def map_gpu(self, ctx, data):
-        return self._map(ctx, data)
-
-    def map_cpu(self, ctx, data):
-        return self._map(ctx, data)
-
-    def job_succeeded(self, jip):
-        if self.out:
-            records.finish_output(self.out)
-
 
 def why_ineligible(out, text=False, base=None):
     """None if GPU RandomWriter takes this job, else the reason it does not."""
     from ..ops import recgen
-    if base is not None and base.get_boolean("mapred.output.compress", False):
-        return "compressed output"
-    if "://" in str(out) and not str(out).startswith("file://"):
-        return f"output directory {out} is not a local one"
-    if text:
-        return recgen.vocabulary_reason(vocabulary())
-    return None
+    why = splits.local_output_reason(out, base)
+    if why is None and text:
+        why = recgen.vocabulary_reason(vocabulary())
+    return why
 
 
 def gpu_job(out, maps=2, bytes_per_map=1 << 20, text=False, seed=0, base=None) -> JobConf:
@@ -189,15 +167,13 @@ def gpu_job(out, maps=2, bytes_per_map=1 << 20, text=False, seed=0, base=None) -
     if why is not None:
         name = "randomtextwriter" if text else "randomwriter"
         raise ValueError(f"{name} into {out!r} is not eligible for the GPU: {why}")
-    job = JobConf(base)
-    job.set_job_name("random-text-writer-gpu" if text else "random-writer-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.randomwrite:RandomWriteSplitJob")
+    job = splits.file_job(base, "random-text-writer-gpu" if text else "random-writer-gpu",
+                          "hbmr.models.randomwrite:RandomWriteSplitJob", output=out,
+                          maps=max(1, maps))
     job.set_boolean(TEXT_KEY, bool(text))
     job.set_long("test.randomtextwrite.bytes_per_map" if text else
                  "test.randomwrite.bytes_per_map", bytes_per_map)
     job.set_long(SEED_KEY, seed)
-    job.set_num_map_tasks(max(1, maps))
     job.set_num_reduce_tasks(0)
-    FileOutputFormat.setOutputPath(job, out)
     recgen.check_params(recgen.TEXT if text else recgen.BYTES, record_params(job, text)[1])
     return job

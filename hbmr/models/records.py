@@ -59,9 +59,9 @@ def is_snappy_compressed(path) -> bool:
     return seqz.file_header(path) is not None
 
 
-def _load(path, start, length, device):
-    """(data, index, compressed): the split, and whether it was decompressed.
-    The file's header is looked at once, here."""
+def load_split_flagged(path, start, length, device):
+    """(data, index, compressed): :func:`load_record_split`, and whether the
+    split was decompressed.  The file's header is looked at once, here."""
     import torch
 
     from ..ops import recsort, seqz
@@ -82,18 +82,7 @@ def load_record_split(path, start, length, device):
     ``recsort.index_records``; of a Snappy RECORD- or BLOCK-compressed file the
     frames of the decompressed records back to back, decoded and assembled on
     the device (``hbmr.ops.seqz.load_split``)."""
-    return _load(path, start, length, device)[:2]
-
-
-def load_job_split(job, key, path, start, length, device):
-    """:func:`load_record_split` for the split ``key`` of ``job``; the bytes a
-    compressed file decoded to are noted for the map's SNAPPY_DECODED_BYTES
-    (``wordcount.count_snappy_decoded``: nothing for a split found resident)."""
-    data, index, compressed = _load(path, start, length, device)
-    if compressed:
-        notes = job.__dict__.setdefault("_snappy_decoded", {})
-        notes[key] = notes.get(key, 0) + int(data.numel())
-    return data, index
+    return load_split_flagged(path, start, length, device)[:2]
 
 
 @contextlib.contextmanager

@@ -20,25 +20,17 @@ this map too.
 """
 from __future__ import annotations
 
-import os
-
 from ..gpu.splitjob import SplitJob
-from ..mapred import FileInputFormat, FileOutputFormat, JobConf
-from . import records
-from .sort import _owned
-from .wordcount import WordCountSplitJob, compressed_input_reason, count_snappy_decoded
+from ..mapred import JobConf
+from . import records, splits
 
 SECONDARYSORT_GROUP = "hbmr.SecondarySortCounters"
 SECONDARYSORT_CPU_FALLBACK_SPLITS = "SECONDARYSORT_CPU_FALLBACK_SPLITS"
-SEPARATOR_KEY = "mapred.textoutputformat.separator"
 
 
-class SecondarySortSplitJob(SplitJob):
+class SecondarySortSplitJob(splits.BothSlots, splits.FinishesOutput, splits.TextSplits, SplitJob):
     collective_reduce = True
     needs_reduce = True
-
-    get_splits = WordCountSplitJob.get_splits
-    load_split = WordCountSplitJob.load_split
 
     def configure(self, conf):
         self.conf = conf
@@ -47,12 +39,11 @@ class SecondarySortSplitJob(SplitJob):
 
     # -- map --------------------------------------------------------------------------
     def _map(self, ctx, data):
-        """The same on both kinds of slot: the ops take the twin for a host
-        tensor, and the irregular flag has one definition."""
+        """The same on both kinds of slot: the irregular flag has one definition."""
         from ..mapred import counters as C
         from ..ops import intpair
         stream = getattr(ctx, "stream", None)
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         parsed = intpair.parse(data, stream)
         keys = parsed.keys
         if parsed.irregular:
@@ -64,31 +55,13 @@ class SecondarySortSplitJob(SplitJob):
         keys, nrec = intpair.sort_keys(keys, self.nparts, stream)
         return {"keys": keys, "records": nrec}
 
-    def map_gpu(self, ctx, data):
-        return self._map(ctx, data)
-
-    def map_cpu(self, ctx, data):
-        return self._map(ctx, data)
-
     # -- shuffle + reduce -------------------------------------------------------------
     def combine(self, ctx, outputs):
-        """The tracker's map outputs regrouped by destination rank: each output
-        is ordered by partition and a rank owns consecutive partitions, so a
-        destination's share of an output is one slice."""
+        """(keys, keys per rank): the map outputs regrouped by destination rank."""
         import torch
-        dev = ctx.device if ctx.device is not None else torch.device("cpu")
-        W = max(1, ctx.world_size)
-        pieces, send = [], []
-        for j in range(W):
-            pa, pb = _owned(j, W, self.nparts)
-            nr = 0
-            for o in outputs:
-                r0, r1 = sum(o["records"][:pa]), sum(o["records"][:pb])
-                pieces.append(o["keys"][r0:r1].to(dev))
-                nr += r1 - r0
-            send.append(nr)
-        keys = torch.cat(pieces) if pieces else torch.empty(0, dtype=torch.int64, device=dev)
-        return keys, send
+        return splits.by_destination(outputs, max(1, ctx.world_size), self.nparts,
+                                     [splits.Field("keys", "records", torch.int64)],
+                                     splits.device_of(ctx))[0]
 
     def reduce(self, ctx, combined):
         from ..mapred import counters as C
@@ -96,7 +69,7 @@ class SecondarySortSplitJob(SplitJob):
         keys, send = combined
         got = ctx.comm.all_to_all_v(keys, send)[0].contiguous()
         got, nrec = intpair.sort_keys(got, self.nparts)
-        pa, pb = _owned(ctx.rank, max(1, ctx.world_size), self.nparts)
+        pa, pb = splits.owned(ctx.rank, max(1, ctx.world_size), self.nparts)
         if sum(nrec[:pa]) or sum(nrec[pb:]):
             raise RuntimeError("records of a partition this rank does not own arrived here")
         groups, r0 = 0, sum(nrec[:pa])
@@ -113,23 +86,10 @@ class SecondarySortSplitJob(SplitJob):
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, n + groups)
         return {"records": n, "groups": groups, "parts": pb - pa}
 
-    def job_succeeded(self, jip):
-        if self.out:
-            records.finish_output(self.out)
-
 
 def why_ineligible(inputs, base=None):
     """None if GPU SecondarySort takes this job, else the reason it does not."""
-    if base is not None and base.get_boolean("mapred.output.compress", False):
-        return "compressed output"
-    if base is not None and base.get(SEPARATOR_KEY, "\t") != "\t":
-        return f"{SEPARATOR_KEY} is not a tab"
-    for f in records.input_files(inputs):
-        if not os.path.isfile(f):
-            return f"input {f} is not a local file"
-        if compressed_input_reason(f) is not None:
-            return compressed_input_reason(f)
-    return None
+    return splits.text_output_reason(base) or splits.text_input_reason(inputs)
 
 
 def gpu_job(inputs, output, reduces=1, base=None, maps=None) -> JobConf:
@@ -140,12 +100,7 @@ def gpu_job(inputs, output, reduces=1, base=None, maps=None) -> JobConf:
     why = why_ineligible(inputs, base)
     if why is not None:
         raise ValueError(f"secondarysort of {inputs!r} is not eligible for the GPU: {why}")
-    job = JobConf(base)
-    job.set_job_name("secondary sort-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.secondarysort:SecondarySortSplitJob")
+    job = splits.file_job(base, "secondary sort-gpu",
+                          "hbmr.models.secondarysort:SecondarySortSplitJob", inputs, output, maps)
     job.set_num_reduce_tasks(max(1, reduces))
-    FileInputFormat.setInputPaths(job, *([inputs] if isinstance(inputs, str) else inputs))
-    FileOutputFormat.setOutputPath(job, output)
-    if maps:
-        job.set_num_map_tasks(maps)
     return job

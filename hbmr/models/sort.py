@@ -21,24 +21,13 @@ maps either.
 """
 from __future__ import annotations
 
-from ..gpu.splitjob import SplitJob, SplitSpec
-from ..mapred import FileInputFormat, FileOutputFormat, JobConf
-from . import records
-from .wordcount import count_snappy_decoded
+from ..gpu.splitjob import SplitJob
+from ..mapred import JobConf
+from . import records, splits
 
 KEY_CLASS_KEY = "hbmr.sort.key.class"
 VALUE_CLASS_KEY = "hbmr.sort.value.class"
 PARTITION_FILE_KEY = "hbmr.sort.partition.file"
-
-
-def owner_of(p, world, nparts):
-    """The rank that sorts and writes partition ``p`` of ``nparts``."""
-    return p * world // nparts
-
-
-def _owned(rank, world, nparts):
-    ps = [p for p in range(nparts) if owner_of(p, world, nparts) == rank]
-    return (ps[0], ps[-1] + 1) if ps else (0, 0)
 
 
 def read_split_points(path, key_class):
@@ -54,7 +43,7 @@ def read_split_points(path, key_class):
     return pts
 
 
-class SortSplitJob(SplitJob):
+class SortSplitJob(splits.BothSlots, splits.FinishesOutput, splits.RecordSplits, SplitJob):
     collective_reduce = True
     needs_reduce = True
 
@@ -76,75 +65,35 @@ class SortSplitJob(SplitJob):
     # -- input ------------------------------------------------------------------------
     def get_splits(self, conf, trackers):
         from ..mapred.formats import SequenceFileInputFormat
-        splits = SequenceFileInputFormat().getSplits(JobConf(conf),
-                                                     max(1, conf.get_num_map_tasks()))
-        out = []
-        for i, s in enumerate(splits):
-            loc = [trackers[i * len(trackers) // len(splits)]] if trackers else []
-            key = f"sort:{s.path}:{s.start}:{s.length}"
-            out.append(SplitSpec(i, key, "file", {"path": s.path, "start": s.start,
-                                                  "length": s.length}, loc, s.length))
-        return out
-
-    def load_split(self, spec: SplitSpec, device):
-        p = spec.params
-        data, index = records.load_job_split(self, spec.key, p["path"], p["start"], p["length"],
-                                             device)
-        return {"data": data, "index": index}
-
-    def load_split_sample(self, spec, device, fraction):
-        split = self.load_split(spec, device)
-        n = max(1, int(split["index"].shape[1] * fraction))
-        return {"data": split["data"], "index": split["index"][:, :n].contiguous()}
-
-    def split_nbytes(self, split) -> int:
-        return int(split["data"].numel() + split["index"].numel() * 8)
+        found = SequenceFileInputFormat().getSplits(JobConf(conf),
+                                                    max(1, conf.get_num_map_tasks()))
+        return [splits.file_spec(i, splits.record_key(s.path, s.start, s.length), s.path, s.start,
+                                 s.length, splits.place(i, len(found), trackers))
+                for i, s in enumerate(found)]
 
     # -- map --------------------------------------------------------------------------
     def _map(self, ctx, split):
-        import torch
-
         from ..mapred import counters as C
         from ..ops import recsort
         data, index = split["data"], split["index"]
         n = int(index.shape[1])
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, n)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         perm, nrec, nbytes, blob = recsort.sort_records(
             data, index, self.nparts, self.split_points, getattr(ctx, "stream", None))
         meta = _meta(index)[perm.to(index.device).long()]
         return {"blob": blob, "meta": meta, "records": nrec, "bytes": nbytes}
 
-    def map_gpu(self, ctx, split):
-        return self._map(ctx, split)
-
-    def map_cpu(self, ctx, split):
-        return self._map(ctx, split)
-
     # -- shuffle + reduce -------------------------------------------------------------
     def combine(self, ctx, outputs):
-        """The tracker's map outputs regrouped by destination rank: each output
-        is ordered by partition and a rank owns consecutive partitions, so a
-        destination's share of an output is one slice."""
+        """(blob, meta, bytes per rank, records per rank): the map outputs
+        regrouped by destination rank."""
         import torch
-        dev = ctx.device if ctx.device is not None else torch.device("cpu")
-        W = max(1, ctx.world_size)
-        blobs, metas, send_bytes, send_recs = [], [], [], []
-        for j in range(W):
-            pa, pb = _owned(j, W, self.nparts)
-            nb = nr = 0
-            for o in outputs:
-                b0, b1 = sum(o["bytes"][:pa]), sum(o["bytes"][:pb])
-                r0, r1 = sum(o["records"][:pa]), sum(o["records"][:pb])
-                blobs.append(o["blob"][b0:b1].to(dev))
-                metas.append(o["meta"][r0:r1].to(dev))
-                nb += b1 - b0
-                nr += r1 - r0
-            send_bytes.append(nb)
-            send_recs.append(nr)
-        blob = torch.cat(blobs) if blobs else torch.empty(0, dtype=torch.uint8, device=dev)
-        meta = torch.cat(metas) if metas else torch.empty((0, 3), dtype=torch.int64, device=dev)
+        (blob, send_bytes), (meta, send_recs) = splits.by_destination(
+            outputs, max(1, ctx.world_size), self.nparts,
+            [splits.Field("blob", "bytes", torch.uint8),
+             splits.Field("meta", "records", torch.int64, (3,))], splits.device_of(ctx))
         return blob, meta, send_bytes, send_recs
 
     def reduce(self, ctx, combined):
@@ -160,7 +109,7 @@ class SortSplitJob(SplitJob):
         foff = torch.cumsum(flen, 0) - flen
         index = torch.stack([foff, flen, foff + rmeta[:, 1], rmeta[:, 2]]).contiguous()
         perm, nrec = recsort.sort_perm(rblob, index, self.nparts, self.split_points)
-        pa, pb = _owned(ctx.rank, max(1, ctx.world_size), self.nparts)
+        pa, pb = splits.owned(ctx.rank, max(1, ctx.world_size), self.nparts)
         if sum(nrec[:pa]) or sum(nrec[pb:]):
             raise RuntimeError("records of a partition this rank does not own arrived here")
         written = 0
@@ -174,10 +123,6 @@ class SortSplitJob(SplitJob):
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_RECORDS, int(perm.numel()))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, written)
         return {"records": written, "parts": pb - pa}
-
-    def job_succeeded(self, jip):
-        if self.out:
-            records.finish_output(self.out)
 
 
 def _meta(index):
@@ -219,17 +164,11 @@ def gpu_job(inputs, output, reduces=1, partition_file=None, base=None, maps=None
     why = why_ineligible(inputs, base, in_format, out_format)
     if why is not None:
         raise ValueError(f"sort of {inputs!r} is not eligible for the GPU: {why}")
-    job = JobConf(base)
-    job.set_job_name("sorter-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.sort:SortSplitJob")
+    job = splits.file_job(base, "sorter-gpu", "hbmr.models.sort:SortSplitJob", inputs, output, maps)
     kc, vc = records.first_classes(records.input_files(inputs))
     job.set(KEY_CLASS_KEY, kc)
     job.set(VALUE_CLASS_KEY, vc)
     job.set_num_reduce_tasks(max(1, reduces))
     if partition_file and reduces > 1:
         job.set(PARTITION_FILE_KEY, partition_file)
-    FileInputFormat.setInputPaths(job, *([inputs] if isinstance(inputs, str) else inputs))
-    FileOutputFormat.setOutputPath(job, output)
-    if maps:
-        job.set_num_map_tasks(maps)
     return job

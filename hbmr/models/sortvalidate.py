@@ -18,11 +18,9 @@ from __future__ import annotations
 
 import os
 
-from ..gpu.splitjob import SplitJob, SplitSpec
-from ..mapred import FileInputFormat, JobConf
-from . import records
-from .sort import SortSplitJob
-from .wordcount import count_snappy_decoded
+from ..gpu.splitjob import SplitJob
+from ..mapred import JobConf
+from . import records, splits
 
 GROUP = "SortValidator"
 SORTED_DIR_KEY = "sortvalidate.sorted.dir"
@@ -31,7 +29,7 @@ TOTAL_ORDER_KEY = "sortvalidate.total.order"
 JOB_NAME = "sortvalidate-gpu"
 
 
-class ValidateSplitJob(SplitJob):
+class ValidateSplitJob(splits.BothSlots, splits.RecordSplits, SplitJob):
     collective_reduce = True
     needs_reduce = False
 
@@ -46,16 +44,9 @@ class ValidateSplitJob(SplitJob):
         """One split per file, the whole file: GPU Sort's key and value for it."""
         from ..mapred.formats import SequenceFileInputFormat
         files = SequenceFileInputFormat().list_status(JobConf(conf))
-        out = []
-        for i, f in enumerate(files):
-            loc = [trackers[i * len(trackers) // len(files)]] if trackers else []
-            out.append(SplitSpec(i, f"sort:{f.path}:0:{f.length}", "file",
-                                 {"path": f.path, "start": 0, "length": f.length}, loc, f.length))
-        return out
-
-    load_split = SortSplitJob.load_split
-    load_split_sample = SortSplitJob.load_split_sample
-    split_nbytes = SortSplitJob.split_nbytes
+        return [splits.file_spec(i, splits.whole_file_key(f.path, f.length), f.path, 0, f.length,
+                                 splits.place(i, len(files), trackers))
+                for i, f in enumerate(files)]
 
     # -- map --------------------------------------------------------------------------
     def side_of(self, path):
@@ -78,7 +69,7 @@ class ValidateSplitJob(SplitJob):
         rep = ctx.reporter
         rep.incrCounter(C.TASK_GROUP, C.MAP_INPUT_RECORDS, n)
         rep.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         rep.incrCounter(GROUP, f"{side}_RECORDS", n)
         rep.incrCounter(GROUP, f"{side}_BYTES", nbytes)
         rep.incrCounter(GROUP, f"{side}_HASH_SUM", hs)
@@ -88,12 +79,6 @@ class ValidateSplitJob(SplitJob):
             if part is not None:
                 rep.incrCounter(GROUP, "MISPARTITIONED_RECORDS", mis)
         return {"records": n}
-
-    def map_gpu(self, ctx, split):
-        return self._map(ctx, split)
-
-    def map_cpu(self, ctx, split):
-        return self._map(ctx, split)
 
 
 def why_ineligible(sort_input, sort_output):
@@ -120,15 +105,13 @@ def gpu_job(sort_input, sort_output, total_order=False, base=None) -> JobConf:
     if why is not None:
         raise ValueError(f"validation of {sort_output!r} against {sort_input!r} is not eligible "
                          f"for the GPU: {why}")
-    job = JobConf(base)
+    job = splits.file_job(base, JOB_NAME, "hbmr.models.sortvalidate:ValidateSplitJob",
+                          [sort_input, sort_output])
     outs = [p for p in os.listdir(sort_output) if p.startswith("part-")]
-    job.set_job_name(JOB_NAME)
-    job.set("hbmr.splitjob.class", "hbmr.models.sortvalidate:ValidateSplitJob")
     job.set(SORTED_DIR_KEY, sort_output)
     job.set_int(REDUCES_KEY, len(outs))
     job.set_boolean(TOTAL_ORDER_KEY, total_order)
     job.set_num_reduce_tasks(0)
-    FileInputFormat.setInputPaths(job, sort_input, sort_output)
     return job
 
 

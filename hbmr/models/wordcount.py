@@ -19,9 +19,11 @@ from __future__ import annotations
 
 from collections import Counter
 
+from ..gpu.splitjob import SplitJob
 from ..io.writable import IntWritable, Text
 from ..mapred import FileInputFormat, FileOutputFormat, JobClient, JobConf, Mapper, Reducer
 from ..mapred.maprunner import MapRunner
+from . import records, splits
 
 INMAPPER_KEY = "hbmr.wordcount.inmapper.combine"
 
@@ -239,94 +241,14 @@ def main(argv=None, cluster=None):
 
 # --------------------------------------------------------------------------- GPU WordCount
 # The same job as a split-level GPU job: a text split
-# is read into HBM with LineRecordReader's boundary rule, tokenized and counted
+# is read into HBM (splits.TextSplits), tokenized and counted
 # by native/kernels/text.hip (exact hash aggregation = the fused combiner), the
 # per-tracker tables are merged and hash-partitioned like HashPartitioner, the
 # shuffle is one all-to-all-v of "word\n" bytes + one of counts (RCCL over
 # xGMI), and each tracker writes its partition sorted by Text key order, in
 # TextOutputFormat's "word\tcount" lines — the classic job's output, byte for
-# byte.  A `.snappy` file is one whole split: it is decoded on the device
-# (hbmr/ops/snappydec.py) and the decoded text is what stays resident.  The
-# loader is shared by GPU Grep, GPU SecondarySort and the word-table jobs.
-from ..gpu.splitjob import SplitJob, SplitSpec  # noqa: E402
-
-
-def read_text_split(path, start, length, chunk=1 << 16) -> bytes:
-    """Bytes of the lines a LineRecordReader over (path, start, length) returns,
-    newlines included: the first partial line is skipped unless start == 0, and
-    the line running through the split end is read to its end."""
-    from ..fs import strip_scheme
-    end = start + length
-    with open(strip_scheme(path), "rb") as f:
-        f.seek(start)
-        begin = start
-        if start != 0:
-            while True:
-                buf = f.read(chunk)
-                if not buf:
-                    return b""
-                i = buf.find(b"\n")
-                if i >= 0:
-                    begin += i + 1
-                    break
-                begin += len(buf)
-        if begin > end:
-            return b""
-        f.seek(begin)
-        body = f.read(end - begin)
-        # finish the line that contains offset `end` (it starts at or before end)
-        tail = []
-        while True:
-            buf = f.read(chunk)
-            if not buf:
-                break
-            i = buf.find(b"\n")
-            if i >= 0:
-                tail.append(buf[:i + 1])
-                break
-            tail.append(buf)
-        return body + b"".join(tail)
-
-
-COMPRESSED_INPUT_GROUP = "hbmr.CompressedInputCounters"
-SNAPPY_DECODED_BYTES = "SNAPPY_DECODED_BYTES"
-
-
-def is_snappy(path) -> bool:
-    """Whether ``path`` carries SnappyCodec's extension: the one codec whose
-    files the split-level text jobs take (decoded by hbmr/ops/snappydec.py)."""
-    from ..io.compress import SnappyCodec, codec_for_path
-    return isinstance(codec_for_path(path), SnappyCodec)
-
-
-def compressed_input_reason(path):
-    """``compressed input <path>`` for a file of any codec but Snappy, else None."""
-    from ..io.compress import codec_for_path
-    if codec_for_path(path) is not None and not is_snappy(path):
-        return f"compressed input {path}"
-    return None
-
-
-def load_text_file(job, key, path, device):
-    """The decoded bytes of the ``.snappy`` file ``path`` on ``device``.  The
-    split ``key`` of ``job`` is noted as decoded here, for the map's counter."""
-    from ..ops import snappydec
-    t = snappydec.decode_file(path, device)
-    notes = job.__dict__.setdefault("_snappy_decoded", {})
-    notes[key] = notes.get(key, 0) + int(t.numel())
-    return t
-
-
-def count_snappy_decoded(job, ctx):
-    """SNAPPY_DECODED_BYTES of a map: what its own load decoded, on the device
-    or in the twin — nothing for a split found resident."""
-    key = (getattr(ctx.spec, "split", None) or {}).get("key")
-    n = job.__dict__.get("_snappy_decoded", {}).pop(key, 0)
-    if n:
-        ctx.reporter.incrCounter(COMPRESSED_INPUT_GROUP, SNAPPY_DECODED_BYTES, n)
-
-
-class WordCountSplitJob(SplitJob):
+# byte.
+class WordCountSplitJob(splits.BothSlots, splits.FinishesOutput, splits.TextSplits, SplitJob):
     collective_reduce = True
     needs_reduce = True
 
@@ -334,116 +256,36 @@ class WordCountSplitJob(SplitJob):
         self.conf = conf
         self.out = conf.get("mapred.output.dir")
 
-    def get_splits(self, conf, trackers):
-        from ..mapred.formats import TextInputFormat
-        from ..mapred.jobconf import JobConf
-        splits = TextInputFormat().getSplits(JobConf(conf), max(1, conf.get_num_map_tasks()))
-        out = []
-        for i, s in enumerate(splits):
-            loc = [trackers[i * len(trackers) // len(splits)]] if trackers else []
-            key = f"wc:{s.path}:{s.start}:{s.length}"
-            out.append(SplitSpec(i, key, "file", {"path": s.path, "start": s.start,
-                                                  "length": s.length}, loc, s.length))
-        return out
-
-    def load_split(self, spec: SplitSpec, device):
-        import torch
-        p = spec.params
-        if is_snappy(p["path"]):
-            # a compressed file is one whole split (TextInputFormat.is_splitable):
-            # no first-line skip; what stays resident under the key is the text
-            return load_text_file(self, spec.key, p["path"], device)
-        data = read_text_split(p["path"], p["start"], p["length"])
-        t = torch.frombuffer(bytearray(data), dtype=torch.uint8) if data else \
-            torch.empty(0, dtype=torch.uint8)
-        return t if str(device) == "cpu" else t.to(device)
-
-    def _count(self, ctx, data):
+    def _map(self, ctx, data):
         from ..mapred import counters as C
         from ..ops import text
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         return text.count_words(data, getattr(ctx, "stream", None))
 
-    def map_gpu(self, ctx, data):
-        return self._count(ctx, data)
-
-    def map_cpu(self, ctx, data):
-        return self._count(ctx, data)
-
     def combine(self, ctx, outputs):
-        import torch
         from ..ops import text
-        dev = ctx.device if ctx.device is not None else torch.device("cpu")
-        blobs = [b.to(dev) for b, _ in outputs]
-        counts = [c.to(dev) for _, c in outputs]
-        blob = torch.cat(blobs) if blobs else torch.empty(0, dtype=torch.uint8, device=dev)
-        cnt = torch.cat(counts) if counts else torch.empty(0, dtype=torch.int64, device=dev)
+        blob, cnt = splits.cat_tables(outputs, splits.device_of(ctx))
         return text.merge_tables(blob, cnt, max(1, ctx.world_size))
 
     def reduce(self, ctx, combined):
         from ..mapred import counters as C
         from ..ops import text
         blob, counts, part_bytes, part_words = combined
-        rblob, rcounts = self._shuffle(ctx, blob, counts, part_bytes, part_words)
+        rblob, rcounts = splits.shuffle_tables(ctx, blob, counts, part_bytes, part_words)
         mblob, mcounts, _, _ = text.merge_tables(rblob, rcounts, 1)
         items = text.sorted_items(mblob, mcounts)
         total = sum(n for _, n in items)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_GROUPS, len(items))
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, len(items))
         if self.out:
-            from . import records
             with records.part_writer(self.out, f"part-{ctx.rank:05d}") as f:
                 f.write(b"".join(w + b"\t" + str(n).encode() + b"\n" for w, n in items))
         return {"distinct": len(items), "words": total}
-
-    @staticmethod
-    def _shuffle(ctx, blob, counts, part_bytes, part_words):
-        """The word tables' shuffle: two static-shape all-to-alls (bytes, then
-        counts) whose slot sizes every rank agrees on through a HOST all-reduce
-        of the largest per-destination sizes (the sizes are host values
-        already: merge_tables returns them), so no collective here waits for
-        the device; the one host read is the compaction after both exchanges
-        are enqueued.  An overflowing slot (impossible with exact maxima, kept
-        as a guard) sends every rank to all_to_all_v (an all-reduced flag)."""
-        import torch
-
-        from ..parallel.collectives import compact_static
-        comm = ctx.comm
-        W = comm.world_size
-        if W <= 1 or not hasattr(comm, "all_to_all_v_static"):
-            return comm.all_to_all_v(blob, part_bytes)[0], comm.all_to_all_v(counts, part_words)[0]
-        mx = torch.tensor([max(part_bytes or [0]), max(part_words or [0])], dtype=torch.int64)
-        mx = comm.all_reduce_max(mx) if hasattr(comm, "all_reduce_max") else mx
-        cap_b, cap_w = max(1, int(mx[0])), max(1, int(mx[1]))
-        rb, rcb = comm.all_to_all_v_static(blob, part_bytes, cap_b)
-        rc, rcw = comm.all_to_all_v_static(counts, part_words, cap_w)
-        got_b = compact_static(rb, rcb, cap_b)
-        got_w = compact_static(rc, rcw, cap_w)
-        # the fallback is a collective: every rank must take it or none (one
-        # rank entering all_to_all_v alone would hang the gang), so the
-        # overflow flags are all-reduced first
-        over = torch.tensor([int(got_b is None or got_w is None)], dtype=torch.int64)
-        if hasattr(comm, "all_reduce_max"):
-            over = comm.all_reduce_max(over)
-        if int(over[0]):
-            return comm.all_to_all_v(blob, part_bytes)[0], comm.all_to_all_v(counts, part_words)[0]
-        return got_b[0], got_w[0]
-
-    def job_succeeded(self, jip):
-        from . import records
-        if self.out:
-            records.finish_output(self.out)
 
 
 def gpu_job(inputs, output, base=None, maps=None) -> JobConf:
     """WordCount as a split-level job (GPU map slots, CPU slots per the hybrid
     cost model)."""
-    job = JobConf(base)
-    job.set_job_name("wordcount-gpu")
-    job.set("hbmr.splitjob.class", "hbmr.models.wordcount:WordCountSplitJob")
-    FileInputFormat.setInputPaths(job, *([inputs] if isinstance(inputs, str) else inputs))
-    FileOutputFormat.setOutputPath(job, output)
-    if maps:
-        job.set_num_map_tasks(maps)
-    return job
+    return splits.file_job(base, "wordcount-gpu", "hbmr.models.wordcount:WordCountSplitJob",
+                           inputs, output, maps)

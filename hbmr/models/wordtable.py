@@ -29,20 +29,15 @@ mapper's own expression and adds 1 to ``WORDTABLE_CPU_FALLBACK_SPLITS``.
 from __future__ import annotations
 
 import collections
-import os
 
 from ..gpu.splitjob import SplitJob, SplitSpec
 from ..io.writable import hash_bytes
-from ..mapred import FileInputFormat, FileOutputFormat, JobConf
-from . import records
-from .sort import owner_of
-from .wordcount import (WordCountSplitJob, compressed_input_reason, count_snappy_decoded,
-                        is_snappy, load_text_file)
+from ..mapred import JobConf
+from . import records, splits
 
 PROGRAM_KEY = "hbmr.wordtable.program"
 WORDTABLE_GROUP = "hbmr.WordTableCounters"
 WORDTABLE_CPU_FALLBACK_SPLITS = "WORDTABLE_CPU_FALLBACK_SPLITS"
-SEPARATOR_KEY = "mapred.textoutputformat.separator"
 HISTOGRAM_ID = b"WORD_HISTOGRAM"
 HISTOGRAM_KEY = b"ValueHistogram:" + HISTOGRAM_ID
 
@@ -78,12 +73,9 @@ def read_files(paths) -> bytes:
     return b"".join(out)
 
 
-class WordTableSplitJob(SplitJob):
+class WordTableSplitJob(splits.BothSlots, splits.FinishesOutput, splits.TextSplits, SplitJob):
     collective_reduce = True
     needs_reduce = True
-
-    _shuffle = staticmethod(WordCountSplitJob._shuffle)
-    job_succeeded = WordCountSplitJob.job_succeeded
 
     def configure(self, conf):
         self.conf = conf
@@ -99,24 +91,24 @@ class WordTableSplitJob(SplitJob):
     # -- input ------------------------------------------------------------------------
     def get_splits(self, conf, trackers):
         if conf.get(PROGRAM_KEY, "wordcount") != "multifilewc":
-            return WordCountSplitJob.get_splits(self, conf, trackers)
+            return super().get_splits(conf, trackers)
         from ..mapred.lib.combine import MultiFileInputFormat
-        splits = MultiFileInputFormat().getSplits(JobConf(conf), max(1, conf.get_num_map_tasks()))
+        found = MultiFileInputFormat().getSplits(JobConf(conf), max(1, conf.get_num_map_tasks()))
         out = []
-        for i, s in enumerate(splits):
-            loc = [trackers[i * len(trackers) // len(splits)]] if trackers else []
+        for i, s in enumerate(found):
             paths = [str(p) for p in s.paths]
             key = "mfwc:" + "|".join(f"{p}:{n}" for p, n in zip(paths, s.lengths))
-            out.append(SplitSpec(i, key, "file", {"paths": paths}, loc,
+            out.append(SplitSpec(i, key, "file", {"paths": paths},
+                                 splits.place(i, len(found), trackers),
                                  sum(int(n) for n in s.lengths)))
         return out
 
     def load_split(self, spec: SplitSpec, device):
         if "paths" not in spec.params:
-            return WordCountSplitJob.load_split(self, spec, device)
+            return super().load_split(spec, device)
         import torch
         paths = spec.params["paths"]
-        if any(is_snappy(p) for p in paths):
+        if any(splits.is_snappy(p) for p in paths):
             return self._load_files_decoded(spec, device)
         data = read_files(paths)
         t = torch.frombuffer(bytearray(data), dtype=torch.uint8) if data else \
@@ -132,8 +124,8 @@ class WordTableSplitJob(SplitJob):
         dev = torch.device(device)
         pieces = []
         for p in spec.params["paths"]:
-            if is_snappy(p):
-                t = load_text_file(self, spec.key, p, device)
+            if splits.is_snappy(p):
+                t = splits.load_text_file(self, spec.key, p, device)
             else:
                 raw = read_files([p])
                 t = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(dev) if raw else None
@@ -152,23 +144,16 @@ class WordTableSplitJob(SplitJob):
 
     # -- map --------------------------------------------------------------------------
     def _map(self, ctx, data):
-        """The same on both kinds of slot: the ops take the twin for a host
-        tensor, and the flag has one definition."""
+        """The same on both kinds of slot: the flag has one definition."""
         from ..mapred import counters as C
         from ..ops import text, wordtab
         ctx.reporter.incrCounter(C.TASK_GROUP, C.MAP_INPUT_BYTES, int(data.numel()))
-        count_snappy_decoded(self, ctx)
+        splits.count_snappy_decoded(self, ctx)
         if self.decoded and wordtab.flag_nonclassic(data):
             ctx.reporter.incrCounter(WORDTABLE_GROUP, WORDTABLE_CPU_FALLBACK_SPLITS, 1)
             blob, counts = text._table_from(classic_words(bytes(data.cpu().numpy())))
             return blob.to(data.device), counts.to(data.device)
         return text.count_words(data, getattr(ctx, "stream", None))
-
-    def map_gpu(self, ctx, data):
-        return self._map(ctx, data)
-
-    def map_cpu(self, ctx, data):
-        return self._map(ctx, data)
 
     # -- shuffle + reduce -------------------------------------------------------------
     def _dest(self, parts, world):
@@ -183,13 +168,8 @@ class WordTableSplitJob(SplitJob):
         (blob, counts, bytes per rank, words per rank)."""
         import torch
         from ..ops import text, wordtab
-        dev = ctx.device if ctx.device is not None else torch.device("cpu")
         W = max(1, ctx.world_size)
-        blobs = [b.to(dev) for b, _ in outputs]
-        counts = [c.to(dev) for _, c in outputs]
-        blob = torch.cat(blobs) if blobs else torch.empty(0, dtype=torch.uint8, device=dev)
-        cnt = torch.cat(counts) if counts else torch.empty(0, dtype=torch.int64, device=dev)
-        buf, us, ul, uc = merge_table(blob, cnt)
+        buf, us, ul, uc = merge_table(*splits.cat_tables(outputs, splits.device_of(ctx)))
         parts = wordtab.partition(buf, us, ul, W if self.histogram else self.nparts,
                                   1 if self.histogram else self.seed)
         dest = self._dest(parts.to(torch.int64), W)
@@ -206,7 +186,7 @@ class WordTableSplitJob(SplitJob):
         from ..ops import wordtab
         blob, counts, send_bytes, send_words = combined
         W = max(1, ctx.world_size)
-        rblob, rcounts = self._shuffle(ctx, blob, counts, send_bytes, send_words)
+        rblob, rcounts = splits.shuffle_tables(ctx, blob, counts, send_bytes, send_words)
         buf, us, ul, uc = merge_table(rblob, rcounts)
         n = int(us.numel())
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_INPUT_GROUPS, n)
@@ -214,18 +194,18 @@ class WordTableSplitJob(SplitJob):
             return self._reduce_histogram(ctx, uc, W)
         parts = wordtab.partition(buf, us, ul, self.nparts, self.seed)
         order, nrec = wordtab.sort_table(buf, us, ul, parts, self.nparts)
-        owned = [p for p in range(self.nparts) if owner_of(p, W, self.nparts) == ctx.rank]
-        if sum(nrec) != sum(nrec[p] for p in owned):
+        pa, pb = splits.owned(ctx.rank, W, self.nparts)
+        if sum(nrec) != sum(nrec[pa:pb]):
             raise RuntimeError("words of a partition this rank does not own arrived here")
         r0 = 0
         for p in range(self.nparts):
-            if p in owned and self.out:
+            if pa <= p < pb and self.out:
                 text = wordtab.format_part(buf, us, ul, uc, order[r0:r0 + nrec[p]].contiguous())
                 with records.part_writer(self.out, f"part-{p:05d}") as f:
                     f.write(text.cpu().numpy().tobytes())       # the part's one copy to the host
             r0 += nrec[p]
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, n)
-        return {"distinct": n, "words": int(uc.sum()) if n else 0, "parts": len(owned)}
+        return {"distinct": n, "words": int(uc.sum()) if n else 0, "parts": pb - pa}
 
     def _reduce_histogram(self, ctx, counts, world):
         import torch
@@ -233,13 +213,13 @@ class WordTableSplitJob(SplitJob):
         from ..ops import wordtab
         values, mult = wordtab.count_runs(wordtab.sort_counts(counts))
         target = (hash_bytes(HISTOGRAM_KEY) & 0x7FFFFFFF) % self.nparts
-        owner = owner_of(target, world, self.nparts)
+        owner = splits.owner_of(target, world, self.nparts)
         runs = torch.stack([values, mult], dim=1).contiguous()
         send = [int(runs.shape[0]) if j == owner else 0 for j in range(world)]
         got = ctx.comm.all_to_all_v(runs, send)[0]
-        owned = [p for p in range(self.nparts) if owner_of(p, world, self.nparts) == ctx.rank]
+        pa, pb = splits.owned(ctx.rank, world, self.nparts)
         written = 0
-        for p in owned:
+        for p in range(pa, pb):
             line = b""
             if p == target and got.shape[0]:
                 report = wordtab.histogram_report(got[:, 0], got[:, 1])
@@ -249,7 +229,7 @@ class WordTableSplitJob(SplitJob):
                 with records.part_writer(self.out, f"part-{p:05d}") as f:
                     f.write(line)
         ctx.reporter.incrCounter(C.TASK_GROUP, C.REDUCE_OUTPUT_RECORDS, written)
-        return {"distinct": int(counts.numel()), "parts": len(owned)}
+        return {"distinct": int(counts.numel()), "parts": pb - pa}
 
 
 def merge_table(blob, counts):
@@ -297,16 +277,7 @@ def why_ineligible(inputs, reduces, base=None):
     """None if the word-table job takes this job, else the reason it does not."""
     if reduces < 1:
         return f"{reduces} reduces: the map output itself is the job's output"
-    if base is not None and base.get_boolean("mapred.output.compress", False):
-        return "compressed output"
-    if base is not None and base.get(SEPARATOR_KEY, "\t") != "\t":
-        return f"{SEPARATOR_KEY} is not a tab"
-    for f in records.input_files(inputs):
-        if not os.path.isfile(f):
-            return f"input {f} is not a local file"
-        if compressed_input_reason(f) is not None:
-            return compressed_input_reason(f)
-    return None
+    return splits.text_output_reason(base) or splits.text_input_reason(inputs)
 
 
 def gpu_job(program, inputs, output, reduces=1, base=None, maps=None) -> JobConf:
@@ -320,15 +291,10 @@ def gpu_job(program, inputs, output, reduces=1, base=None, maps=None) -> JobConf
     why = why_ineligible(inputs, reduces, base)
     if why is not None:
         raise ValueError(f"{program} of {inputs!r} is not eligible for the GPU: {why}")
-    job = JobConf(base)
-    job.set_job_name(PROGRAMS[program][0])
-    job.set("hbmr.splitjob.class", "hbmr.models.wordtable:WordTableSplitJob")
+    job = splits.file_job(base, PROGRAMS[program][0], "hbmr.models.wordtable:WordTableSplitJob",
+                          inputs, output, maps)
     job.set(PROGRAM_KEY, program)
     job.set_num_reduce_tasks(reduces)
-    FileInputFormat.setInputPaths(job, *([inputs] if isinstance(inputs, str) else inputs))
-    FileOutputFormat.setOutputPath(job, output)
-    if maps:
-        job.set_num_map_tasks(maps)
     return job
 
 

@@ -9,6 +9,7 @@ instead of silently falling back to a PyTorch path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import threading
@@ -330,3 +331,16 @@ def stream_handle(stream=None) -> int:
     if stream is None:
         stream = torch.cuda.current_stream()
     return int(stream.cuda_stream)
+
+
+def is_cuda(t_or_device) -> bool:
+    """Whether a tensor lies on a GPU, or a device (or its name) is one."""
+    return torch.device(getattr(t_or_device, "device", t_or_device)).type == "cuda"
+
+
+def stream_ctx(stream, t=None):
+    """Enters ``stream``; nothing for None (the caller's current stream), or
+    for a ``t`` (tensor or device) that is not on a GPU: the twin's path."""
+    if stream is not None and (t is None or is_cuda(t)):
+        return torch.cuda.stream(stream)
+    return contextlib.nullcontext()

@@ -341,9 +341,9 @@ def count_gpu(tab, prefixes, stream=None, levels=DEFAULT_LEVELS, capacity=DEFAUL
     ``on_launch(kind, level, nstates)`` is called before each kernel group;
     ``stats``: a dict that gets ``placements``, the tree nodes the count
     kernel made (a device synchronise)."""
-    import contextlib
-
     import torch
+
+    from . import _lib
     device = torch.device("cuda" if device is None else device)
     counts = torch.zeros(len(prefixes), dtype=torch.int64, device=device)
     if not tab.solvable or not len(prefixes):
@@ -363,7 +363,7 @@ def count_gpu(tab, prefixes, stream=None, levels=DEFAULT_LEVELS, capacity=DEFAUL
         for part in expand_gpu(tab, words, capacity):
             descend(part, level + 1)
 
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+    with _lib.stream_ctx(stream):
         start = torch.from_numpy(first).to(device)
         for a in range(0, len(prefixes), capacity):
             descend(start[a:a + capacity], 0)

@@ -34,8 +34,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .recsort import _stream_ctx
 from .sort import gather_u64, radix_sort_keys, radix_sort_pairs
+from .wordtab import offsets
 
 SKIP, RECORD, IRREGULAR = 0, 1, 2
 SEPARATOR_LINE = b"-" * 48 + b"\n"          # SEPARATOR of examples/secondarysort.py and '\n'
@@ -50,10 +50,6 @@ _POW10 = 10 ** np.arange(10, dtype=np.int64)
 Parsed = collections.namedtuple("Parsed", "keys lines irregular")
 Parsed.__doc__ = """``keys`` int64[records] in line order, ``lines`` the split's
 line count, ``irregular`` whether the split needs :func:`parse_slow`."""
-
-
-def _is_cuda(t):
-    return t.device.type == "cuda"
 
 
 def _check_bytes(data):
@@ -102,11 +98,11 @@ def line_starts(data, stream=None):
     split and whether a byte >= 0x80 occurs."""
     _check_bytes(data)
     n = int(data.numel())
-    if not _is_cuda(data):
+    if not _lib.is_cuda(data):
         b = data.numpy()
         return torch.from_numpy(_line_starts_np(b)), bool(b.size and b.max() >= 0x80)
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         st = _lib.stream_handle(stream)
         dev = data.device
         if n == 0:
@@ -187,11 +183,11 @@ def _parse_lines(data, starts, stream):
     L = int(starts.numel())
     if starts.dtype != torch.int32 or starts.device != data.device or L > data.numel():
         raise ValueError("starts: int32[lines] on the data's device required")
-    if not _is_cuda(data):
+    if not _lib.is_cuda(data):
         status, keys = _parse_lines_np(data.numpy(), starts.numpy())
         return torch.from_numpy(status), torch.from_numpy(keys), None, None
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         dev = data.device
         status = torch.empty(L, dtype=torch.uint8, device=dev)
         keys = torch.empty(L, dtype=torch.int64, device=dev)
@@ -208,11 +204,11 @@ def _parse_lines(data, starts, stream):
 def compact(status, keys, block_counts=None, stream=None, scan=None):
     """int64[records]: the keys of the RECORD lines, in line order (``scan``:
     :func:`_excl_scan` of ``block_counts`` where the caller has it)."""
-    if not _is_cuda(keys):
+    if not _lib.is_cuda(keys):
         return keys[status == RECORD].contiguous()
     lib = _lib.load()
     L = int(keys.numel())
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         base, nrec = scan if scan is not None else _excl_scan(block_counts)
         out = torch.empty(nrec, dtype=torch.int64, device=keys.device)
         rc = lib.hbmr_intpair_compact(_lib.ptr(status), _lib.ptr(keys), L, _lib.ptr(base), nrec,
@@ -228,7 +224,7 @@ def parse(data, stream=None):
     if flag is None:
         irregular = non_ascii or bool((status == IRREGULAR).any())
         return Parsed(compact(status, keys), int(starts.numel()), irregular)
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         incl = torch.cumsum(bc, 0, dtype=torch.int64)
         nrec, bad = torch.stack([incl[-1], flag[0].long()]).tolist() if bc.numel() else (0, 0)
         out = compact(status, keys, bc, stream, ((incl - bc).contiguous(), nrec))
@@ -262,9 +258,9 @@ def partition(keys, nparts, stream=None):
     nparts = int(nparts)
     if nparts < 1:
         raise ValueError("at least one partition required")
-    if not _is_cuda(keys):
+    if not _lib.is_cuda(keys):
         return torch.from_numpy(np.abs(firsts(keys.numpy()) * 127) % nparts)
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         parts = torch.empty_like(keys)
         rc = _lib.load().hbmr_intpair_partition(_lib.ptr(keys), int(keys.numel()), nparts,
                                                 _lib.ptr(parts), _lib.stream_handle(stream))
@@ -279,13 +275,13 @@ def sort_keys(keys, nparts, stream=None):
     _check_keys(keys)
     nparts = int(nparts)
     n = int(keys.numel())
-    if not _is_cuda(keys):
+    if not _lib.is_cuda(keys):
         k = keys.numpy().view(np.uint64)
         p = partition(keys, nparts).numpy()
         order = np.lexsort((k, p))
         return (torch.from_numpy(k[order].view(np.int64).copy()),
                 np.bincount(p, minlength=nparts).tolist())
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         keys = radix_sort_keys(keys.clone(), 0, 64, stream)
         if nparts == 1 or n == 0:
             return keys, [n] + [0] * (nparts - 1)
@@ -326,24 +322,17 @@ def lengths(keys, stream=None):
     line, and in front of a group head the separator line."""
     _check_keys(keys)
     n = int(keys.numel())
-    if not _is_cuda(keys):
+    if not _lib.is_cuda(keys):
         k = keys.numpy()
         ln = _chars_np(firsts(k)) + _chars_np(seconds(k)) + 2 + \
             _heads_np(k) * len(SEPARATOR_LINE)
         return torch.from_numpy(ln.astype(np.int32))
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         lens = torch.empty(n, dtype=torch.int32, device=keys.device)
         rc = _lib.load().hbmr_intpair_lengths(_lib.ptr(keys), n, _lib.ptr(lens),
                                               _lib.stream_handle(stream))
         _lib.check(rc, "hbmr_intpair_lengths")
         return lens
-
-
-def offsets(lens):
-    """int64[n + 1]: the exclusive scan of :func:`lengths`, the total last."""
-    offs = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=lens.device)
-    torch.cumsum(lens, 0, dtype=torch.int64, out=offs[1:])
-    return offs
 
 
 def _digits_np(v):
@@ -388,7 +377,7 @@ def fill(keys, offs, out, stream=None):
         raise ValueError("offs: int64[n + 1] on the keys' device required")
     if n == 0:
         return out
-    with _stream_ctx(stream if _is_cuda(keys) else None):
+    with _lib.stream_ctx(stream, keys):
         if int(offs[0]) != 0 or int(offs[-1]) > out.numel() or \
                 bool((offs[1:] - offs[:-1] != lengths(keys, stream)).any()):
             raise ValueError("offs is not the scan of the records' lengths within the buffer")
@@ -399,13 +388,13 @@ def _fill(keys, offs, out, stream):
     n = int(keys.numel())
     if n == 0:
         return out
-    if not _is_cuda(keys):
+    if not _lib.is_cuda(keys):
         k, o, dst = keys.numpy(), offs.numpy(), out.numpy()
         for a in range(0, n, _BATCH):
             z = min(n, a + _BATCH)
             dst[o[a]:o[z]] = _fill_np(k[a:z], a == 0 or (k[a] >> 32) != (k[a - 1] >> 32))
         return out
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         rc = _lib.load().hbmr_intpair_fill(_lib.ptr(keys), _lib.ptr(offs), n, _lib.ptr(out),
                                            _lib.stream_handle(stream))
         _lib.check(rc, "hbmr_intpair_fill")
@@ -415,7 +404,7 @@ def _fill(keys, offs, out, stream):
 def format_part(keys, stream=None):
     """(text uint8[bytes], groups): a part's output from its sorted keys."""
     _check_keys(keys)
-    with _stream_ctx(stream if _is_cuda(keys) else None):
+    with _lib.stream_ctx(stream, keys):
         lens = lengths(keys, stream)
         offs = offsets(lens)
         total, groups = torch.stack([offs[-1], (lens > RECORD_MAX).sum()]).tolist()

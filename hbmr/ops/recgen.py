@@ -313,10 +313,6 @@ def _fill_cpu(kind, S, first, index, out, params, voc):
 
 
 # --------------------------------------------------------------------------- ops
-def _is_cuda(device):
-    return torch.device(device).type == "cuda"
-
-
 def _ranges(params):
     lo_k, hi_k, lo_v, hi_v = params
     return lo_k, hi_k - lo_k + 1, lo_v, hi_v - lo_v + 1
@@ -332,10 +328,10 @@ def lengths(kind, seed, m, first, count, params, device="cpu", vocabulary=None, 
     if first < 0 or count < 0 or count >= 1 << 31:
         raise ValueError("record range outside [0, 2^31)")
     S = split_word(seed, m)
-    if not _is_cuda(device):
+    if not _lib.is_cuda(device):
         return torch.from_numpy(_lengths_cpu(kind, S, int(first), count, params, voc))
     lib = _lib.load()
-    with recsort._stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         out = torch.empty((4, count), dtype=torch.int64, device=device)
         woff = voc.on(device)[1] if voc is not None else None
         rc = lib.hbmr_recgen_lengths(S, int(first), count, int(kind == TEXT), *_ranges(params),
@@ -367,7 +363,7 @@ def plan(kind, seed, m, first, target, params, device="cpu", pos=0, last_sync=0,
     batch = min(_MAX_BATCH, max(64, int(target / _mean_payload(kind, params, voc) * 1.05) + 16))
     if max_bytes is not None:
         batch = min(batch, max(64, int(max_bytes) // 16))
-    with recsort._stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         while target > 0:
             L = lengths(kind, seed, m, first + done, batch, params, device, voc, stream)
             pay = torch.cumsum(L[KL] + L[VL], 0) + paid
@@ -429,7 +425,7 @@ def fill(kind, seed, m, first, index, out, params=None, vocabulary=None, stream=
         _fill_cpu(kind, S, int(first), index.numpy(), out.numpy(), params, voc)
         return out
     lib = _lib.load()
-    with recsort._stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         st = _lib.stream_handle(stream)
         if kind == BYTES:
             base, entry, total = recsort._chunk_table(foff, flen, out,
@@ -460,7 +456,7 @@ def fill_syncs(out, gaps, escape, stream=None):
         return out
     if gaps.min() < 0 or gaps.max() + recsort.SYNC_SIZE > out.numel():
         raise ValueError("a sync hole lies outside the buffer")
-    with recsort._stream_ctx(stream if out.device.type == "cuda" else None):
+    with _lib.stream_ctx(stream, out):
         at = torch.from_numpy(gaps[:, None] + np.arange(recsort.SYNC_SIZE)).reshape(-1)
         esc = torch.frombuffer(bytearray(escape), dtype=torch.uint8).repeat(gaps.size)
         out[at.to(out.device)] = esc.to(out.device)
@@ -474,8 +470,8 @@ def generate(kind, seed, m, first, target, params, device="cpu", pos=0, last_syn
     the sync holes hold zeros on the host and are unset on a GPU."""
     voc = _vocab(kind, vocabulary)
     p = plan(kind, seed, m, first, target, params, device, pos, last_sync, voc, max_bytes, stream)
-    with recsort._stream_ctx(stream if _is_cuda(device) else None):
-        data = torch.empty(p.total, dtype=torch.uint8, device=device) if _is_cuda(device) else \
+    with _lib.stream_ctx(stream, device):
+        data = torch.empty(p.total, dtype=torch.uint8, device=device) if _lib.is_cuda(device) else \
             torch.zeros(p.total, dtype=torch.uint8)
     fill(kind, seed, m, first, p.index, data, params, voc, stream)
     if escape is not None:

@@ -30,7 +30,7 @@ import torch
 
 from . import _lib
 from . import recsort
-from .recsort import FLEN, FOFF, KLEN, KOFF, _ptr, _rows, _stream_ctx
+from .recsort import FLEN, FOFF, KLEN, KOFF, _ptr, _rows
 
 OPS = ("inner", "outer", "override")
 MAX_SOURCES = 8
@@ -185,7 +185,7 @@ def group_heads(data, index, stream=None, check=True):
     keys; ``bad`` = the first record whose key is below its predecessor's, or
     None for sorted input."""
     rows = _validate(data, index) if check else _rows(index)
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         head, bad = _heads(data, rows, stream)
         b = int(bad.item())
     return head, (None if b == -1 else b)
@@ -210,7 +210,7 @@ def rank_heads(probe, target, stream=None, check=True, thk=None):
     _, _, pkoff, pklen = _rows(pindex)
     _, _, tkoff, tklen = _rows(tindex)
     gp, gt = int(prec.numel()), int(trec.numel())
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         lb = torch.zeros(gp, dtype=torch.int32, device=pdata.device)
         eq = torch.zeros(gp, dtype=torch.int32, device=pdata.device)
         if gp == 0 or gt == 0:
@@ -246,7 +246,7 @@ def plan(sources, op, stream=None, stats=None):
     tuples, OverflowError."""
     S = len(sources)
     dev = sources[0][0].device
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         rows = [_validate(d, i) for d, i in sources]
         gfirst, gcnt = [], []
         heads = [_heads(data, r, stream) for (data, _), r in zip(sources, rows)]
@@ -387,7 +387,7 @@ class _Emitter:
         p, S, T = self.p, self.S, hi - lo
         if not 0 <= lo <= hi <= p.total or T > _MAX_CHUNK_TUPLES:
             raise ValueError(f"tuple range [{lo}, {hi}) of {p.total}")
-        with _stream_ctx(self.stream):
+        with _lib.stream_ctx(self.stream):
             tkey = torch.empty(T, dtype=torch.int32, device=self.dev)
             trec = torch.empty((S, T), dtype=torch.int32, device=self.dev)
             tlen = torch.empty(T, dtype=torch.int64, device=self.dev)
@@ -406,7 +406,7 @@ class _Emitter:
         p, S = self.p, self.S
         tkey, trec, tlen = expanded
         T = int(tkey.numel())
-        with _stream_ctx(self.stream):
+        with _lib.stream_ctx(self.stream):
             dst_off = dst_off.contiguous()
             if bool(((dst_off < 0) | (dst_off + tlen > out.numel())).any()):
                 raise ValueError("join frames: a frame lies outside the output buffer")
@@ -425,7 +425,7 @@ class _Emitter:
     def copy(self, pieces, out):
         """The piece copy into ``out``: chunk table, then one launch."""
         psrc, plen, pdst = pieces
-        with _stream_ctx(self.stream):
+        with _lib.stream_ctx(self.stream):
             cbase, entry, total = recsort._chunk_table(pdst, plen, out, skip_empty=True)
             if total:
                 rc = _lib.load().hbmr_recjoin_copy(_ptr(psrc), _ptr(plen), _ptr(pdst), _ptr(cbase),
@@ -436,7 +436,7 @@ class _Emitter:
     def fill(self, expanded, dst_off, out_bytes, out=None):
         """uint8[out_bytes] with the expanded tuples' frames at ``dst_off``
         (int64[T], device); bytes no frame covers are left unset."""
-        with _stream_ctx(self.stream):
+        with _lib.stream_ctx(self.stream):
             if out is None:
                 out = torch.empty(out_bytes, dtype=torch.uint8, device=self.dev)
             if expanded[0].numel():
@@ -451,7 +451,7 @@ def _cuts(em: _Emitter, chunk_bytes):
     out = []
     if p.total == 0:
         return out
-    with _stream_ctx(em.stream):
+    with _lib.stream_ctx(em.stream):
         kbytes, bound = em.key_bytes()
         cum = torch.cat([kbytes.new_zeros(1), torch.cumsum(kbytes, 0)])
         budget = float(max(1, chunk_bytes))
@@ -523,10 +523,10 @@ def join_chunks(sources, op, headers=None, chunk_bytes=CHUNK_BYTES_DEFAULT, stre
         ex = em.expand(lo, hi)
 
         def body(dst, total, ex=ex):
-            with _stream_ctx(stream):    # the copies to and from the host too
+            with _lib.stream_ctx(stream):    # the copies to and from the host too
                 dst_t = torch.from_numpy(np.ascontiguousarray(dst, dtype=np.int64)).to(em.dev)
                 return em.fill(ex, dst_t, total).cpu().numpy()
-        with _stream_ctx(stream):
+        with _lib.stream_ctx(stream):
             flen = ex[2].cpu().numpy()
         yield Chunk(flen, body)
 

@@ -19,7 +19,6 @@ On a GPU the native library must load (no silent fallback).
 from __future__ import annotations
 
 import bisect
-import contextlib
 import ctypes
 import os
 
@@ -205,10 +204,6 @@ def sort_records_cpu(data, index, nparts, split_points=None):
 _ptr = _lib.ptr
 
 
-def _stream_ctx(stream):
-    return torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()
-
-
 def _rows(index):
     if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != 4:
         raise ValueError("index int64[4, n] required")
@@ -281,7 +276,7 @@ def sort_perm(data, index, nparts, split_points=None, stream=None, stats=None, p
         perm, part_records, _, _ = sort_records_cpu(data, index, nparts, split_points)
         return perm, part_records
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         st = _lib.stream_handle(stream)
         nb = data.numel()
         if bool(((koff < 0) | (klen < 0) | (koff + klen > nb) | (foff < 0) | (flen < 0) |
@@ -384,7 +379,7 @@ def gather_frames(data, order, foff, flen, dst_off, out_bytes, stream=None, chec
             out[d:d + ln] = src[s:s + ln]
         return torch.from_numpy(out)
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         if out is None:
             out = torch.empty(out_bytes, dtype=torch.uint8, device=dev)
         elif out.dtype != torch.uint8 or out.numel() != out_bytes or out.device != dev or \
@@ -413,7 +408,7 @@ def sort_records(data, index, nparts, split_points=None, stream=None, stats=None
     foff, flen, koff, klen = _rows(index)
     perm, part_records = sort_perm(data, index, nparts, split_points, stream, stats)
     n = int(perm.numel())
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         if n == 0:
             return perm, part_records, [0] * nparts, torch.empty(0, dtype=torch.uint8,
                                                                  device=data.device)

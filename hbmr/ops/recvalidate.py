@@ -145,7 +145,7 @@ def validate_records(data, index, order=False, nparts=1, part=None, stream=None,
         return res + (check_sorted_part_cpu(data, index, nparts, part) if order or part is not None
                       else (0, 0))
     lib = _lib.load()
-    with recsort._stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         foff, flen, koff, klen = _check_index(data, index)
         n = int(foff.numel())
         st = _lib.stream_handle(stream)

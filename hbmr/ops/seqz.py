@@ -29,7 +29,6 @@ import numpy as np
 import torch
 
 from . import _lib, recsort, snappydec
-from .recsort import _stream_ctx
 
 RECORD, BLOCK = 1, 2
 SNAPPY = "org.apache.hadoop.io.compress.SnappyCodec"
@@ -211,7 +210,7 @@ def decode_lengths(cols, blocks, n, stream=None, _blocks_dev=None, status=None, 
         raise ValueError("cols: contiguous uint8[bytes] on a GPU required")
     if _blocks_dev is None:
         _check_blocks(blocks, int(cols.numel()), n)
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         outs = []
         for t in (klen, vlen):
             if t is None:
@@ -241,7 +240,7 @@ def build_index(cols, bdev, klen, vlen, status, prefix, stream=None):
     status.  Device work only."""
     n = int(klen.numel())
     nb = int(bdev.shape[1])
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         rec_block = torch.repeat_interleave(torch.arange(nb, device=cols.device), bdev[0],
                                             output_size=n)
         ok = status[rec_block] == 0
@@ -277,7 +276,7 @@ def assemble(out, foff, klen, vlen, keys, ksrc, vals=None, vsrc=None, stream=Non
                 t.device != out.device or t.device.type != "cuda":
             raise ValueError("assemble: contiguous uint8[bytes] on one GPU required")
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         if vals is None:
             rc = lib.hbmr_seqblock_heads(_ptr(keys), int(keys.numel()), _ptr(ksrc), _ptr(foff),
                                          _ptr(klen), _ptr(vlen), n, _ptr(out), int(out.numel()),
@@ -359,7 +358,7 @@ def load_split(path, start, length, device, stream=None, stages=None, header=Non
         stages.append((what, a, b))
         return out
 
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         dev = host.to(device)
         cdev = dev[where[0][0]:where[1][0]].view(torch.int64)
         tdev = dev[where[1][0]:tbytes].view(torch.int64).view(table.shape)

@@ -27,7 +27,6 @@ import torch
 
 from ..io import snappy
 from . import _lib
-from .recsort import _stream_ctx
 
 _INDEX = None
 
@@ -90,7 +89,7 @@ def decode_chunks(src, table, out=None, stream=None, _table_dev=None):
     if src.device.type != "cuda":
         return out, _decode_chunks_host(src, table, out)
     lib = _lib.load()
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         status = torch.empty(n, dtype=torch.int32, device=src.device)
         if n:
             tdev = _table_dev if _table_dev is not None else \
@@ -150,7 +149,7 @@ def decode_file(path, device, stream=None):
     h = host.numpy()
     h[:32 * n] = table.numpy().reshape(-1).view(np.uint8)
     h[32 * n:] = np.frombuffer(data, dtype=np.uint8)
-    with _stream_ctx(stream):
+    with _lib.stream_ctx(stream):
         dev = host.to(device)
         tdev = dev[:32 * n].view(torch.int64)
         out = torch.empty(total, dtype=torch.uint8, device=device)

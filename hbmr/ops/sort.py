@@ -51,10 +51,6 @@ def sort_window(hi_range=None):
 _ptr = _lib.ptr
 
 
-def _on_gpu(t):
-    return t.device.type == "cuda"
-
-
 # --------------------------------------------------------------------------- radix sort
 def _window_order_np(keys: torch.Tensor, begin_bit: int, end_bit: int):
     """CPU twin of both radix sorts: (keys as uint64, their stable order by
@@ -74,7 +70,7 @@ def radix_sort_pairs(keys: torch.Tensor, vals: torch.Tensor, begin_bit: int = 0,
         raise ValueError("keys int64[n], vals int32[n] required")
     if n <= 1:
         return
-    if not _on_gpu(keys):
+    if not _lib.is_cuda(keys):
         k, order = _window_order_np(keys, begin_bit, end_bit)
         keys.copy_(torch.from_numpy(k[order].view(np.int64).copy()))
         vals.copy_(vals[torch.from_numpy(order)])
@@ -120,7 +116,7 @@ def radix_sort_keys(keys: torch.Tensor, begin_bit: int = 0, end_bit: int = 64, s
         raise ValueError("keys int64[n] required")
     if n <= 1:
         return keys
-    if not _on_gpu(keys):
+    if not _lib.is_cuda(keys):
         k, order = _window_order_np(keys, begin_bit, end_bit)
         keys.copy_(torch.from_numpy(k[order].view(np.int64).copy()))
         return keys
@@ -212,7 +208,7 @@ def teragen(first_row: int, nrows: int, device="cuda", stream=None) -> torch.Ten
 def tera_keys(records: torch.Tensor, stream=None):
     """(hi, lo) int64 tensors: key bytes 0-7 and 8-9 as big-endian unsigned ints."""
     n, stride = records.shape
-    if _on_gpu(records):
+    if _lib.is_cuda(records):
         hi = torch.empty(n, dtype=torch.int64, device=records.device)
         lo = torch.empty(n, dtype=torch.int64, device=records.device)
         rc = _lib.load().hbmr_tera_keys(_ptr(records), n, stride, _ptr(hi), _ptr(lo),
@@ -229,7 +225,7 @@ def tera_keys(records: torch.Tensor, stream=None):
 
 def gather_records(records: torch.Tensor, perm: torch.Tensor, stream=None) -> torch.Tensor:
     n, rb = records.shape
-    if not _on_gpu(records):
+    if not _lib.is_cuda(records):
         return records[perm.long()]
     out = torch.empty_like(records)
     rc = _lib.load().hbmr_gather_records(_ptr(records), _ptr(perm), n, rb, _ptr(out),
@@ -240,7 +236,7 @@ def gather_records(records: torch.Tensor, perm: torch.Tensor, stream=None) -> to
 
 def gather_u64(src: torch.Tensor, perm: torch.Tensor, stream=None) -> torch.Tensor:
     """dst[i] = src[perm[i]] for int64 storage (perm int32)."""
-    if not _on_gpu(src):
+    if not _lib.is_cuda(src):
         return src[perm.long()]
     dst = torch.empty(perm.numel(), dtype=src.dtype, device=src.device)
     rc = _lib.load().hbmr_gather_u64(_ptr(src), _ptr(perm), perm.numel(), _ptr(dst),
@@ -252,7 +248,7 @@ def gather_u64(src: torch.Tensor, perm: torch.Tensor, stream=None) -> torch.Tens
 def sort_keys(hi: torch.Tensor, lo: torch.Tensor, stream=None):
     """Permutation ordering records by (hi, lo) unsigned; returns (perm, hi_sorted, lo_sorted)."""
     n = hi.numel()
-    if not _on_gpu(hi):
+    if not _lib.is_cuda(hi):
         h = hi.numpy().view(np.uint64)
         lw = lo.numpy().view(np.uint64)
         order = np.lexsort((lw, h)).astype(np.int32)
@@ -294,7 +290,7 @@ def split_offsets(hi: torch.Tensor, lo: torch.Tensor, split_hi: torch.Tensor,
     R-1 splitters (partition p holds keys in [split[p-1], split[p]))."""
     n = hi.numel()
     nparts = split_hi.numel() + 1
-    if not _on_gpu(hi):
+    if not _lib.is_cuda(hi):
         h = hi.numpy().view(np.uint64)
         lw = lo.numpy().view(np.uint64)
         sh = split_hi.numpy().view(np.uint64)
@@ -324,7 +320,7 @@ def count_unsorted_dev(hi: torch.Tensor, lo: torch.Tensor, stream=None) -> torch
     n = hi.numel()
     if n <= 1:
         return torch.zeros((), dtype=torch.int64, device=hi.device)
-    if not _on_gpu(hi):
+    if not _lib.is_cuda(hi):
         h = hi.numpy().view(np.uint64)
         lw = lo.numpy().view(np.uint64)
         bad = (h[:-1] > h[1:]) | ((h[:-1] == h[1:]) & (lw[:-1] > lw[1:]))
@@ -347,7 +343,7 @@ def tera_keys_part(records: torch.Tensor, split_hi: torch.Tensor, split_lo: torc
     number of splitters <= key; splitters sorted).  CPU only: the twin that
     CPU :func:`tera_partition` is built on and the reference its GPU form is
     tested against."""
-    if _on_gpu(records):
+    if _lib.is_cuda(records):
         raise ValueError("tera_keys_part is the CPU twin: tera_partition runs on the GPU")
     ns = split_hi.numel()
     hi, lo = tera_keys(records)
@@ -395,7 +391,7 @@ def tera_partition(records: torch.Tensor, split_hi: torch.Tensor, split_lo: torc
     n, stride = records.shape
     ns = split_hi.numel()
     nparts = ns + 1
-    if not _on_gpu(records):
+    if not _lib.is_cuda(records):
         hi, lo, pid = tera_keys_part(records, split_hi, split_lo)
         order = torch.from_numpy(np.argsort(pid.numpy(), kind="stable"))
         counts = torch.bincount(pid, minlength=nparts)
@@ -436,7 +432,7 @@ def merge_runs(runs, stream=None):
     if not runs:
         return (torch.empty(0, dtype=torch.int64), torch.empty(0, dtype=torch.int64),
                 torch.empty(0, dtype=torch.int32))
-    if not _on_gpu(runs[0][0]):
+    if not _lib.is_cuda(runs[0][0]):
         h = torch.cat([r[0] for r in runs]).numpy().view(np.uint64)
         lw = torch.cat([r[1] for r in runs]).numpy().view(np.uint64)
         v = torch.cat([r[2] for r in runs])
@@ -503,7 +499,7 @@ def tera_collect(his, los, rows, starts, lens, with_keys=True, stream=None):
     S = len(rows)
     n = int(sum(lens))
     dev = rows[0].device
-    if not _on_gpu(rows[0]):
+    if not _lib.is_cuda(rows[0]):
         sel = [slice(int(a), int(a) + int(m)) for a, m in zip(starts, lens)]
         split = torch.cat([torch.full((int(m),), s, dtype=torch.int32) for s, m in enumerate(lens)])
         row = torch.cat([r[sl] for r, sl in zip(rows, sel)])
@@ -539,7 +535,7 @@ def tera_collect_slots(rows, starts: torch.Tensor, pre: torch.Tensor, cap: int, 
     S = len(rows)
     W = pre.shape[0]
     dev = rows[0].device
-    if not _on_gpu(rows[0]):
+    if not _lib.is_cuda(rows[0]):
         split = torch.full((W * cap,), -1, dtype=torch.int32)   # NO_SPLIT's bits
         row = torch.zeros(W * cap, dtype=torch.int32)
         st, pr = starts.tolist(), pre.tolist()
@@ -614,7 +610,7 @@ def tera_collect_gid(his, rows, starts, lens, stream=None, window: KeyWindow | N
         raise ValueError(f"at most {GID_MAX_SPLITS} map outputs per packed-id collect")
     n = int(sum(lens))
     dev = rows[0].device
-    if not _on_gpu(rows[0]):
+    if not _lib.is_cuda(rows[0]):
         sel = [slice(int(a), int(a) + int(m)) for a, m in zip(starts, lens)]
         gid = torch.cat([(r[sl].to(torch.int64) | (s << 24)).to(torch.int32)
                          for s, (r, sl) in enumerate(zip(rows, sel))])
@@ -649,7 +645,7 @@ def gather_records_gid(bases, gid: torch.Tensor, stream=None, keys=None,
     n = gid.numel()
     rb = bases[0].shape[1]
     packed = gid.dtype == torch.int64
-    if not _on_gpu(gid):
+    if not _lib.is_cuda(gid):
         g = gid.to(torch.int64) & 0xFFFFFFFF
         s, r = g >> 24, g & 0xFFFFFF
         res = torch.empty(n, rb, dtype=torch.uint8)
@@ -707,7 +703,7 @@ def sort_gathered(his, rows, starts, lens, bases, stream=None, hi_range=None, de
             pieces = [h[int(a):int(a) + int(m)] ^ _SIGN for h, a, m in zip(his, starts, lens)
                       if int(m)]
             mm = torch.stack([torch.stack([p.min(), p.max()]) for p in pieces]) ^ _SIGN
-            if _on_gpu(mm):
+            if _lib.is_cuda(mm):
                 mm = mm.cpu()
             mu = mm.numpy().view(np.uint64)
             lo_b = int(mu[:, 0].min()) if lo_b is None else lo_b
@@ -716,7 +712,7 @@ def sort_gathered(his, rows, starts, lens, bases, stream=None, hi_range=None, de
         h, _ = tera_collect_gid(his, rows, starts, lens, stream=stream, window=kw)
         radix_sort_keys(h, 32, 64, stream=stream)
         lo = torch.empty_like(h)
-        win = torch.empty(n, dtype=torch.int32, device=h.device) if _on_gpu(h) else None
+        win = torch.empty(n, dtype=torch.int32, device=h.device) if _lib.is_cuda(h) else None
         # each record's id is read from its packed word before the gather
         # writes the record's full hi key over it (and its window into win)
         recs = gather_records_gid(bases, h, stream=stream, keys=(h, lo), win=win)
@@ -729,7 +725,7 @@ def sort_gathered(his, rows, starts, lens, bases, stream=None, hi_range=None, de
         lo = torch.empty_like(h)
         recs = gather_records_gid(bases, gid, stream=stream, keys=(h, lo))
         del gid
-    if not _on_gpu(recs):
+    if not _lib.is_cuda(recs):
         order = np.lexsort((lo.numpy().view(np.uint64), h.numpy().view(np.uint64)))
         o = torch.from_numpy(order)
         if defer:
@@ -760,7 +756,7 @@ def gather_records_multi(bases, split: torch.Tensor, row: torch.Tensor, perm=Non
     gathered from several split tensors in one pass."""
     n = split.numel()
     rb = bases[0].shape[1]
-    if not _on_gpu(split):
+    if not _lib.is_cuda(split):
         k = perm.long() if perm is not None else torch.arange(n)
         s, r = split[k].long(), row[k].long()
         res = torch.empty(n, rb, dtype=torch.uint8) if out is None else out
@@ -789,7 +785,7 @@ def tera_group_stats(hi: torch.Tensor, lo: torch.Tensor, prev, acc: torch.Tensor
     n = hi.numel()
     if n == 0:
         return
-    if not _on_gpu(hi):
+    if not _lib.is_cuda(hi):
         bad = count_unsorted(hi, lo)
         if prev is not None:
             bad += int(pair_greater(prev, (hi[:1], lo[:1])))

@@ -23,8 +23,6 @@ must load (no silent fallback).
 """
 from __future__ import annotations
 
-import contextlib
-
 import numpy as np
 import torch
 
@@ -40,15 +38,6 @@ def seed_of(prefix: bytes) -> int:
     """The hash state after ``prefix``: :func:`partition`'s seed for keys that
     are ``prefix + word``.  ``seed_of(b"") == 1``."""
     return hash_bytes(prefix) & 0xFFFFFFFF
-
-
-def _is_cuda(t):
-    return t.device.type == "cuda"
-
-
-def _stream_ctx(t, stream):
-    return torch.cuda.stream(stream) if stream is not None and _is_cuda(t) else \
-        contextlib.nullcontext()
 
 
 def _check_table(buf, starts, lens, counts=None):
@@ -101,10 +90,10 @@ def partition(buf, starts, lens, nparts, seed=1, stream=None):
     nparts, seed = int(nparts), int(seed) & 0xFFFFFFFF
     if nparts < 1:
         raise ValueError("at least one partition required")
-    if not _is_cuda(buf):
+    if not _lib.is_cuda(buf):
         return torch.tensor([partition_of(w, nparts, seed) for w in words_of(buf, starts, lens)],
                             dtype=torch.int32)
-    with _stream_ctx(buf, stream):
+    with _lib.stream_ctx(stream, buf):
         parts = torch.empty(n, dtype=torch.int32, device=buf.device)
         rc = _lib.load().hbmr_wordtab_partition(_lib.ptr(buf), _lib.ptr(starts), _lib.ptr(lens), n,
                                                 seed, nparts, _lib.ptr(parts),
@@ -145,11 +134,11 @@ def line_lengths(lens, counts, order=None, stream=None):
             counts.device != lens.device:
         raise ValueError("lens int32[n] and counts int64[n] on one device required")
     m = _check_order(order, n, lens.device)
-    if not _is_cuda(lens):
+    if not _lib.is_cuda(lens):
         sel = slice(None) if order is None else order.numpy().astype(np.int64)
         return torch.from_numpy((lens.numpy()[sel].astype(np.int64) + 2 +
                                  _chars_np(counts.numpy()[sel])).astype(np.int32))
-    with _stream_ctx(lens, stream):
+    with _lib.stream_ctx(stream, lens):
         out = torch.empty(m, dtype=torch.int32, device=lens.device)
         rc = _lib.load().hbmr_wordtab_lengths(_lib.ptr(lens.contiguous()),
                                               _lib.ptr(counts.contiguous()), _lib.ptr(order), m,
@@ -158,11 +147,11 @@ def line_lengths(lens, counts, order=None, stream=None):
     return out
 
 
-def offsets(line_lens):
-    """int64[m + 1]: the exclusive scan of :func:`line_lengths`, the total last
-    (64 bits: a part may exceed 2 GiB)."""
-    offs = torch.zeros(line_lens.numel() + 1, dtype=torch.int64, device=line_lens.device)
-    torch.cumsum(line_lens, 0, dtype=torch.int64, out=offs[1:])
+def offsets(lens):
+    """int64[n + 1]: the exclusive scan of the line lengths ``lens``, the total
+    last (64 bits: a part may exceed 2 GiB)."""
+    offs = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=lens.device)
+    torch.cumsum(lens, 0, dtype=torch.int64, out=offs[1:])
     return offs
 
 
@@ -170,14 +159,14 @@ def _fill(buf, starts, lens, counts, order, offs, total, out, stream):
     m = offs.numel() - 1
     if m == 0 or total == 0:
         return out
-    if not _is_cuda(buf):
+    if not _lib.is_cuda(buf):
         words = words_of(buf, starts, lens)
         cs = counts.tolist()
         ids = range(m) if order is None else order.tolist()
         text = b"".join(b"%s\t%d\n" % (words[i], cs[i]) for i in ids)
         out.numpy()[:total] = np.frombuffer(text, dtype=np.uint8)
         return out
-    with _stream_ctx(buf, stream):
+    with _lib.stream_ctx(stream, buf):
         rc = _lib.load().hbmr_wordtab_fill(_lib.ptr(buf), _lib.ptr(starts), _lib.ptr(lens),
                                            _lib.ptr(counts), _lib.ptr(order), _lib.ptr(offs), m,
                                            total, _lib.ptr(out), _lib.stream_handle(stream))
@@ -199,7 +188,7 @@ def fill_lines(buf, starts, lens, counts, order, offs, out, stream=None):
         raise ValueError("offs: contiguous int64[m + 1] on the table's device required")
     if m == 0:
         return out
-    with _stream_ctx(buf, stream):
+    with _lib.stream_ctx(stream, buf):
         total = int(offs[-1])
         if int(offs[0]) != 0 or total > out.numel() or \
                 bool((offs[1:] - offs[:-1] != line_lengths(lens, counts, order, stream)).any()):
@@ -212,7 +201,7 @@ def format_part(buf, starts, lens, counts, order=None, stream=None):
     all, in table order), back to back."""
     n = _check_table(buf, starts, lens, counts)
     _check_order(order, n, buf.device)
-    with _stream_ctx(buf, stream):
+    with _lib.stream_ctx(stream, buf):
         offs = offsets(line_lengths(lens, counts, order, stream))
         total = int(offs[-1])
         out = torch.empty(total, dtype=torch.uint8, device=buf.device)
@@ -225,9 +214,9 @@ def sort_counts(counts, stream=None):
     sort of :mod:`hbmr.ops.sort` on a GPU."""
     if counts.dtype != torch.int64 or counts.dim() != 1:
         raise ValueError("counts: int64[n] required")
-    if not _is_cuda(counts) or counts.numel() == 0:
+    if not _lib.is_cuda(counts) or counts.numel() == 0:
         return torch.sort(counts).values
-    with _stream_ctx(counts, stream):
+    with _lib.stream_ctx(stream, counts):
         return _sort.radix_sort_keys(counts.clone(), 0, 64, stream)
 
 

@@ -23,6 +23,7 @@ from hbmr.mapred.cluster import LocalCluster
 from hbmr.mapred.task import TaskReporter
 from hbmr.models import randomwrite as write_job
 from hbmr.models import records
+from hbmr.models import sort as sort_job
 from hbmr.models import sortvalidate as validate_job
 from hbmr.ops import recgen, recsort
 
@@ -360,7 +361,7 @@ def test_resident_split_equals_indexer(tmp_path, text):
     # the key is GPU Sort's and GPU SortValidator's for the file
     conf = sort_example.make_job(str(tmp_path / "o"), str(tmp_path / "sorted"))
     conf.set_num_map_tasks(1)
-    assert [s.key for s in validate_job.SortSplitJob().get_splits(conf, [])] == \
+    assert [s.key for s in sort_job.SortSplitJob().get_splits(conf, [])] == \
         [f"sort:{part}:0:{size}"]
     _, ctx, _ = _run_map(tmp_path / "p", text, 4, 1, 50_000,
                         keys={write_job.RESIDENT_KEY: "false"})

@@ -21,6 +21,7 @@ from hbmr.io.writable import BytesWritable, IntWritable, Text
 from hbmr.mapred import JobClient, JobConf
 from hbmr.mapred.cluster import LocalCluster
 from hbmr.mapred.lib.basic import HashPartitioner
+from hbmr.models import sort as sort_job
 from hbmr.models import sortvalidate as validate_job
 from hbmr.ops import recsort, recvalidate
 
@@ -331,7 +332,7 @@ def test_job_splits_are_whole_files_under_sort_keys(sorted_dirs):
     # GPU Sort's own key for a file it reads as one split
     sort_conf = sort_example.make_job(inp, out + "x")
     sort_conf.set_num_map_tasks(1)
-    sort_splits = validate_job.SortSplitJob().get_splits(sort_conf, [])
+    sort_splits = sort_job.SortSplitJob().get_splits(sort_conf, [])
     assert {s.key for s in sort_splits} == {s.key for s in splits if "/in/" in s.key}
     assert sj.side_of(files[0]) == ("IN", None)
     assert sj.side_of(os.path.join(out, "part-00002")) == ("OUT", 2)

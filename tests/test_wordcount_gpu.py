@@ -12,6 +12,7 @@ from hbmr.mapred import JobClient, JobConf
 from hbmr.mapred.cluster import LocalCluster
 from hbmr.mapred.formats import FileSplit, LineRecordReader
 from hbmr.models import wordcount
+from hbmr.models.splits import read_text_split
 from hbmr.ops import text
 
 
@@ -43,7 +44,7 @@ def test_read_text_split_matches_line_record_reader(tmp_path):
         got, want = [], []
         for start in range(0, size, split):
             length = min(split, size - start)
-            got.append(wordcount.read_text_split(path, start, length))
+            got.append(read_text_split(path, start, length))
             rr = LineRecordReader(JobConf(), FileSplit(path, start, length))
             lines = []
             while True:

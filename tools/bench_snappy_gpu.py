@@ -36,6 +36,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hbmr.io import snappy  # noqa: E402
 from hbmr.mapred import JobConf  # noqa: E402
 from hbmr.mapred.cluster import LocalCluster  # noqa: E402
+from hbmr.models import splits  # noqa: E402
 from hbmr.models import wordcount as wc_model  # noqa: E402
 from hbmr.ops import snappydec  # noqa: E402
 
@@ -198,7 +199,7 @@ def end_to_end(nbytes, files, tmp):
             rj = wc_model.run(inp, os.path.join(tmp, f"gpu-{run}"), 1, cluster=cl, gpu=True)
             res[f"gpu_{run}_s"] = round(time.perf_counter() - t, 3)
             res[f"gpu_{run}_decoded_bytes"] = rj.getCounters().get(
-                wc_model.COMPRESSED_INPUT_GROUP, wc_model.SNAPPY_DECODED_BYTES)
+                splits.COMPRESSED_INPUT_GROUP, splits.SNAPPY_DECODED_BYTES)
     with LocalCluster(JobConf(), num_trackers=1, cpu_slots=8) as cl:
         t = time.perf_counter()
         wc_model.run(inp, os.path.join(tmp, "classic"), 1, cluster=cl)
